@@ -6,8 +6,13 @@ In-Next-Week 01 LBVH scene: 10k random moving spheres (seed 1234), 19
 500 spp, 50 bounces (In-Next-Week/base.h:148-173, 01_BoundingVolumeHierarchy/computeShaderSrc.glsl).
 One step = one full frame: every pixel, every sample, every bounce of the reference's INW-01 loop.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|ns]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|ns] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes work
+of its own: the CPU baseline (the oracle on the host cores, 10-20 s) and the line's `parity` of
+the timed frame against it.  --dump-outputs DIR writes the last timed frame (DIR/rgba.npy,
+DIR/depth.npy) so that two builds can be compared output for output.
 
 Secondary lines: --config c2 (configs[1]: In-One-Weekend 03 final scene, 1200x800, 100 spp) and
 --config ns (the north star's IOW-03 final scene at 1920x1080, 500 spp).
@@ -261,6 +266,38 @@ def block_parity(rect, ref_rgba, ref_depth, img, dep) -> dict:
             "oracle": "oracle/librt_oracle.so render of the same block at the same spp (the cpu_baseline run)"}
 
 
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: what one run may write in all
+DUMP_SEED = 20250131     # --dump-outputs: the pixel sample of a frame larger than that
+
+
+def dump_outputs(dirname: str, frames: dict) -> dict:
+    """--dump-outputs: write the last timed frame, {name: device tensor [H, W] or [H, W, C]} over the
+    same H x W pixels, as DIR/<name>.npy in float32.  A frame above DUMP_BYTES in all is written as
+    a fixed seeded sample of its pixels instead: the same pixels of every array, in raster order
+    ([k] or [k, C]), with their raster indices y * W + x in DIR/pixel_index.npy (float64).
+    Returns {file name: shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    frames = {k: v for k, v in frames.items() if v is not None}
+    H, W = next(iter(frames.values())).shape[:2]
+    per_pixel = sum(4 * int(np.prod(v.shape[2:], dtype=np.int64)) for v in frames.values())
+    idx = None
+    if H * W * per_pixel > DUMP_BYTES:
+        k = (DUMP_BYTES - 4096) // (per_pixel + 8)  # 8: the index; 4096: the .npy headers
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, size=k, replace=False))
+    written = {}
+    for name, v in frames.items():
+        v = v.to(torch.float32)
+        if idx is not None:
+            v = v.reshape(H * W, *v.shape[2:])[torch.from_numpy(idx).to(v.device)]
+        a = np.ascontiguousarray(v.cpu().numpy(), np.float32)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+    if idx is not None:
+        np.save(os.path.join(dirname, "pixel_index.npy"), idx.astype(np.float64))
+        written["pixel_index.npy"] = [len(idx)]
+    return written
+
+
 def apply_opts(opts):
     """--opt FIELD=VALUE: set rt_options fields (rejecting names the struct lacks)."""
     if not opts:
@@ -351,6 +388,8 @@ def main_group(args):
         "timed_region": "rt_render_multi_async of one full frame per step: every device's share, the grouped "
                         "RCCL send/recv of colour + depth + counters to device 0, its unpack kernel",
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rgba": img, "depth": dep})
     print(json.dumps(out), flush=True)
     if args.save_image:
         np.save(args.save_image, img.cpu().numpy())
@@ -371,7 +410,15 @@ def main():
     ap.add_argument("--cpu-spp", type=int, default=0,
                     help="CPU baseline samples per pixel (default: the config's spp)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="host cores for the CPU baseline (default: nproc)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (the oracle on the "
+                         "host cores, on the frame's central block) and the line's `parity` of the timed frame "
+                         "against it; a plain run reports both as null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 writes the last timed frame as DIR/rgba.npy and (INW) "
+                         "DIR/depth.npy, float32, at most 64 MB in all (a larger frame: a fixed seeded sample "
+                         "of its pixels, named by DIR/pixel_index.npy)")
     ap.add_argument("--balance", action="store_true",
                     help="multi-rank: deal the timed frames' tiles by LPT over the warm-up frame's tile costs "
                          "(measured neutral on the 8-way frames: their time is set by long samples, not by rays)")
@@ -437,6 +484,8 @@ def main():
     if shard and world == 1:
         part, nparts = (int(v) for v in shard.split("/"))
         T = tile_for(nparts)
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: a shard run (RT_BENCH_SHARD) assembles no frame")
     nx, ny = math.ceil(W / T), math.ceil(H / T)
     allt = deal_order(nx, ny, nparts)
     lists = [allt[r::nparts] for r in range(nparts)]  # the hashed deal (first frame)
@@ -712,7 +761,7 @@ def main():
             except Exception:  # noqa: BLE001
                 ref_walk = None
         cpu, parity = None, None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cores = args.cpu_threads or host_cores()
             # ~10-20 s of host work on the GPU box (C3: 3.2 Mrays/s on 16 cores for the central block)
             if cfg == "c3":
@@ -823,6 +872,8 @@ def main():
             cyc = dict(zip(("camera", "closest_hit", "bvh_walk", "leaf_tests", "segment", "coop_query", "coop_shade",
                             "coop_pop"), d[8:16]))
             out["wave_cycles_share"] = {k: round(v / max(1, cyc["camera"] + cyc["segment"]), 4) for k, v in cyc.items()}
+        if args.dump_outputs:  # the last timed frame as rank 0 assembled it in its step
+            dump_outputs(args.dump_outputs, {"rgba": image[:H, :W], "depth": dimage[:H, :W] if inw else None})
         print(json.dumps(out), flush=True)
         if args.save_image:
             np.save(args.save_image, image[:H, :W].cpu().numpy())

@@ -114,3 +114,54 @@ def test_opt_rejects_unknown_fields(monkeypatch):
     monkeypatch.setattr(bench.R, "set_options", no_device)
     with pytest.raises(SystemExit, match="inw_wide_wlak"):
         bench.main()
+
+
+def test_dump_outputs_whole_frame(tmp_path):
+    """bench.py --dump-outputs: a frame within the size bound is written whole, float32, one file per
+    array; an absent array (IOW-03 has no depth image) writes no file."""
+    import torch
+    rng = np.random.default_rng(3)
+    rgba = rng.random((27, 48, 4), dtype=np.float32)
+    rgba[5, 7, 2] = np.nan
+    depth = rng.random((27, 48), dtype=np.float32)
+    d = str(tmp_path / "out")
+    w = bench.dump_outputs(d, {"rgba": torch.from_numpy(rgba), "depth": torch.from_numpy(depth)})
+    assert w == {"rgba.npy": [27, 48, 4], "depth.npy": [27, 48]}
+    got = np.load(os.path.join(d, "rgba.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), rgba.view(np.uint32))
+    assert np.array_equal(np.load(os.path.join(d, "depth.npy")), depth)
+    d2 = str(tmp_path / "iow")
+    assert bench.dump_outputs(d2, {"rgba": torch.from_numpy(rgba), "depth": None}) == {"rgba.npy": [27, 48, 4]}
+    assert sorted(os.listdir(d2)) == ["rgba.npy"]
+    # a padded frame cropped to W x H (a non-contiguous view), as main() passes it
+    pad = torch.zeros((64, 64, 4))
+    pad[:27, :48] = torch.from_numpy(rgba)
+    bench.dump_outputs(d2, {"rgba": pad[:27, :48], "depth": None})
+    assert np.array_equal(np.load(os.path.join(d2, "rgba.npy")).view(np.uint32), rgba.view(np.uint32))
+
+
+def test_dump_outputs_samples_a_large_frame(tmp_path, monkeypatch):
+    """Above the bound the same seeded pixels of every array are written, in raster order, with
+    their indices; the files stay within the bound and the sample is the same from run to run."""
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40_000)
+    H, W = 50, 70  # 3500 pixels x 20 B = 70,000 B > the bound
+    rng = np.random.default_rng(4)
+    rgba = rng.random((H, W, 4), dtype=np.float32)
+    depth = rng.random((H, W), dtype=np.float32)
+    frames = {"rgba": torch.from_numpy(rgba), "depth": torch.from_numpy(depth)}
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    w = bench.dump_outputs(a, frames)
+    bench.dump_outputs(b, frames)
+    files = sorted(os.listdir(a))
+    assert files == ["depth.npy", "pixel_index.npy", "rgba.npy"] and set(w) == set(files)
+    assert sum(os.path.getsize(os.path.join(a, f)) for f in files) <= 40_000
+    idx = np.load(os.path.join(a, "pixel_index.npy"))
+    k = len(idx)
+    assert idx.dtype == np.float64 and 0 < k < H * W and k >= (40_000 - 4096) // 28 - 1
+    i = idx.astype(np.int64)
+    assert np.all(np.diff(i) > 0) and i[0] >= 0 and i[-1] < H * W
+    assert np.array_equal(np.load(os.path.join(a, "rgba.npy")), rgba.reshape(-1, 4)[i])
+    assert np.array_equal(np.load(os.path.join(a, "depth.npy")), depth.reshape(-1)[i])
+    for f in files:
+        assert open(os.path.join(a, f), "rb").read() == open(os.path.join(b, f), "rb").read(), f

@@ -11,7 +11,7 @@ TAG=${TAG:-$CFG}
 X=${BENCH_ARGS:-}
 O=gpurun_out/prof_$TAG
 rm -rf $O && mkdir -p $O
-timeout -k 10 500 python3 bench.py --config $CFG --steps ${STEPS:-10} $X > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 500 python3 bench.py --full --config $CFG --steps ${STEPS:-10} $X > $O/bench.json 2> $O/bench.err || exit 1
 ARGS="--config $CFG --steps 1 --warmup 1 --no-cpu-baseline $X"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt -o run --output-format csv -- python3 bench.py $ARGS > $O/kt.log 2>&1 || exit 1
 i=0
