@@ -1,0 +1,128 @@
+/* Diagnostics, bench and test hooks of librt_hip.so: every rt_debug_* entry point.  Not part
+ * of the render ABI a host needs (rt_hip.h); the symbols, signatures and struct layouts are
+ * covered by the same RT_ABI_VERSION. */
+#ifndef RT_HIP_DEBUG_H
+#define RT_HIP_DEBUG_H
+
+#include "rt_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The path the scene's last render took (bench line): the main kernel as
+ * rocprofv3 names it and its launches per frame, the resolved fold order and which exact
+ * shortcuts were on for that frame (some are decided per frame: the probe's pick, the fused
+ * cull's error bound, the beam lists' memory and geometry conditions).  Synchronises when the
+ * fold order was left to the device probe. */
+typedef struct rt_path_info {
+    char kernel[64];
+    int launches;
+    int order;            /* INW: 1 pixel-major, 2 sample-major, 3 per-pixel k_inw; IOW-03: 4 sample-parallel, 5 sequential */
+    int order_forced;     /* 1 when rt_options.inw_order chose it, 0 when the probe did */
+    int wide_walk, beams, ri_grid, fused_cull;
+    int lds_nodes;        /* wide BVH nodes staged in LDS (0: none) */
+    int claim_order;
+    int ring_entries;     /* fold window of the kernel that ran */
+    int iow_bvh;          /* IOW-03: 0 linear loop, 1 culling BVH, 2 culling BVH in LDS */
+    int ring_lds;         /* 1: the fold ring was in LDS (k_inw_pm: inw_ring_pm = 0; k_inw_sm: inw_ring_sm = 0 and a BVH top of <= 5 nodes) */
+    int stackless;        /* 1: the reference LBVH walks ran stackless where no push could drop */
+    int lbvh_lds_nodes;   /* LBVH nodes the stackless walks read from LDS (no wide walk) */
+    int qnodes;           /* 1: the wide closest-hit walks read quantised nodes (inw_qnodes) */
+    int global_stack;     /* 1: the reference's 40-float stacks lived in global memory, not in LDS */
+    int walk_stack;       /* entries of the wide walks' own node stack per lane (LDS) */
+    uint64_t ref_walks;   /* INW: the last frame's closest-hit queries (segments + shadow rays) that the wide
+                             walk or beam list handed to the reference's LBVH walks (stackless or stack) */
+    int time_bins;        /* INW: time-bin culling trees the wide closest-hit walks chose from (0: the swept
+                             tree; inw_time_bins, moving objects, walks that read no LDS-staged nodes) */
+    int beam_bins;        /* INW: beam lists per pixel (one per time bin; 0: one list over the swept boxes) */
+    int sphere_records;   /* INW: 1 when the object tests read the sphere records (inw_sphere_records) */
+} rt_path_info;
+int rt_debug_path(rt_dev_scene *s, rt_path_info *out);
+
+/* ---- diagnostics ---------------------------------------------------------------------
+ * d_buf: device array of 16 uint64 (or NULL to disable).  While set, the IOW-03 kernel adds
+ *   [0..7]  per wave iteration of each phase (outer work loop, BVH walk, postponed-leaf tests,
+ *           ray segments): 1 and the number of lanes taking part (lane occupancy);
+ *   [8..13] wave shader-clock cycles in: the work loop's camera-ray part, closest-hit queries,
+ *           their BVH walk, leaf tests, ray segments, (unused).
+ * Diagnostics cost time; never enable them for a measured run. */
+int rt_debug_counters(uint64_t *d_buf);
+/* d_buf: device array with one uint32 per work unit (or NULL to disable): the IOW-03 kernel
+ * writes the rays each pixel cast when the pixel completes (unit = tile-major pixel index in
+ * tile mode, 8x8-block-major in rect mode).  The INW fold kernels instead ADD the rays of each
+ * output pixel (index = the pixel's position in the output image: y * W + x, or the packed
+ * tile index), so the buffer must be zeroed before the render. */
+int rt_debug_pixel_rays(uint32_t *d_buf);
+/* Lanes parked by each tail-compaction round of the scene's last render (synchronises the
+ * device).  Returns the number of rounds written to out (<= cap). */
+int rt_debug_rounds(rt_dev_scene *s, uint32_t *out, int cap);
+/* Rays per sample over the scene's last sample-parallel IOW-03 render (synchronises):
+ * out[0] = max, out[1] = samples, out[2+b] = samples with 2^b <= rays < 2^(b+1),
+ * out[34+b] = rays in those samples.  66 entries. */
+int rt_debug_spec_hist(rt_dev_scene *s, uint64_t *out);
+/* Per pixel unit of the last sample-parallel IOW-03 render, 4 x u32: sample-0 rays, the most
+ * rays of one sample, that sample's index, and (column 3 of row r) the pixel at rank r of the
+ * heaviest-first order.  Returns the number of units (<= cap_units) or an error. */
+int rt_debug_spec_pixels(rt_dev_scene *s, uint32_t *out, uint32_t cap_units);
+/* Same 66 x u64 layout as rt_debug_spec_hist, over the samples of group 0's last re-execution
+ * list (their final executions). */
+int rt_debug_spec_list_hist(rt_dev_scene *s, uint64_t *out);
+/* With RT_DEBUG_FIRST_STALE=1 (which repurposes the stack-drop counter): out[b] / out[16+b] =
+ * samples / rays of the re-execution list whose first stale stack read came in the b-th 16th
+ * of their segments. */
+int rt_debug_spec_list_stale(rt_dev_scene *s, uint64_t *out);
+/* Rays of every (pixel unit, sample) record of the last sample-parallel IOW-03 render
+ * (rays_out[s * P + pu], cap >= P * S), group 0's last re-execution list (up to list_cap
+ * units) and dims = {P, S, list count, sequential-leftover count}. */
+int rt_debug_spec_dump(rt_dev_scene *s, uint32_t *rays_out, size_t cap, uint32_t *list_out, uint32_t list_cap,
+                       uint32_t *dims);
+/* With RT_DEBUG_TIMES=1 set before the render: per (pixel unit, sample) record of the last
+ * sample-parallel IOW-03 render, start_out[s * P + pu] = launch of the sample's last start
+ * (bits 0-15) and its start count (bits 16-31), end_out = launch it finished in (synchronises). */
+int rt_debug_spec_times(rt_dev_scene *s, uint32_t *start_out, uint32_t *end_out, size_t cap);
+/* Main render kernel of the scene's last render and how many times it was launched (the
+ * bench's per-launch roofline figures divide by this).  Returns the count; writes the name. */
+int rt_debug_launches(rt_dev_scene *s, char *name_out, int name_cap);
+/* Sample chunks of the scene's last render: the sample-parallel paths split the samples into
+ * chunks whose records fit the device's free memory (INW: RT_SPEC_MAX_GB), and the per-pixel
+ * paths split them by chunk_plan.  1 = one pass over all samples. */
+int rt_debug_chunks(rt_dev_scene *s);
+/* Kernel timing (diagnostics / bench): with rt_debug_time_kernels(1), every launch of the main
+ * sample-parallel IOW-03 kernel (rt_debug_launches' name) is bracketed by HIP events on its
+ * stream; rt_debug_kernel_time returns the summed durations and the launch count of the
+ * scene's last render (waits for it). */
+int rt_debug_time_kernels(int on);
+/* Numerics self-check of the shortened correctly rounded sequences in rt_math.hpp against the
+ * compiler's, for all 2^32 float bit patterns x: which 0 = rcp_sqrt_domain(sqrtf(x)) (the
+ * reciprocal normalize() uses) vs 1.0f / sqrtf(x); other values are RT_E_ARG.
+ * Writes the mismatch count and the lowest mismatching x (0xffffffff if none); synchronous. */
+int rt_debug_check_fastmath(int which, uint64_t *mismatches, uint32_t *first_bad);
+int rt_debug_kernel_time(rt_dev_scene *s, double *ms_total, int *launches);
+/* The INW scene's walk structures (synchronises): info = {wide nodes, dfs_high, wide depth, RI grid
+ * built, RI cells, stackless layout, objects, where the walk structures were built: 0 host, 1 device,
+ * 2 host after the device build ran past its level cap}; rank_out (2n, may be NULL) receives the objects'
+ * depth-first ranks (invert 0, then 1) when the wide walk is built.  Lets the tests compare the
+ * device build (rt_dev_scene_inw_update) with the host build of a fresh scene. */
+int rt_debug_wide_info(rt_dev_scene *s, uint32_t info[8], uint32_t *rank_out);
+/* Test hook: the device build of the walk structures (rt_dev_scene_inw_update) launches at most
+ * `levels` SAH / collapse levels (0 = its own cap, 256); a deeper tree is built on the host instead
+ * (rt_debug_wide_info info[7] = 2), which lets a test reach that fallback with an ordinary scene. */
+int rt_debug_build_level_cap(int levels);
+/* Test hooks for the host build of the time-bin culling trees and the sphere records (no device;
+ * DESIGN.md §5.2).  rt_debug_time_bins builds the wide walk's trees from the reference's LBVH nodes
+ * and GeometryBuff records (28 floats each) with `bins` time bins and copies the 4-wide nodes (40
+ * floats each, links as int bits) into wnodes_out when wnodes_cap holds them; info = {nodes of the
+ * swept tree, bins built (1: none), nodes per bin tree, all nodes}.  rt_debug_bin_boxes writes the
+ * culling boxes (lo xyz, hi xyz per object) of bin b of `bins`.  rt_debug_sphere_records writes the
+ * 3-float4 sphere records (12 floats per object) and returns 1, or 0 when some object does not
+ * qualify. */
+int rt_debug_time_bins(const float *nodes, const float *geom, uint32_t n, uint32_t bins, float *wnodes_out,
+                       uint32_t wnodes_cap, uint32_t info[4]);
+int rt_debug_bin_boxes(const float *geom, uint32_t n, uint32_t bins, uint32_t b, float *boxes_out);
+int rt_debug_sphere_records(const float *geom, uint32_t n, int layout, float *out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* RT_HIP_DEBUG_H */

@@ -1,4 +1,4 @@
-// rt_capi.hip -- implementation of include/rt_hip.h and include/rt_scene.h.
+// rt_capi.hip -- implementation of include/rt_hip.h, include/rt_hip_debug.h and include/rt_scene.h.
 //
 // Owns device memory, converts the reference's record layouts into the kernels' device
 // layouts (hot/cold split, per-object reciprocals hoisted under the numerics contract),
@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/rt_hip.h"
+#include "../../include/rt_hip_debug.h"
 #include "../../include/rt_scene.h"
 #include "rt_host.hpp"
 #include "rt_kernels.hpp"
@@ -628,11 +629,7 @@ int update_inw(rt_dev_scene *s, const float *geom, uint32_t n, const float *node
     const size_t nbytes = size_t(2 * n - 1) * 8 * sizeof(float);
     std::vector<float> host_nodes;
     if (!nodes) {  // ConstructLBVH_Buff on the device (rt_lbvh_build_async), read back for the host builders
-        if (s->nodes.bytes < nbytes) {
-            s->nodes.~DevBuf();
-            new (&s->nodes) DevBuf();
-            HIP_OK(s->nodes.alloc(nbytes));
-        }
+        HIP_OK(s->nodes.reserve(nbytes));
         HIP_OK(s->aabb.store(aabbs, size_t(n) * 6 * sizeof(float)));
         const size_t ws = rtk::lbvh_workspace_bytes(n);
         HIP_OK(s->lbvh_ws.reserve(ws));
@@ -981,11 +978,7 @@ int launch_scene_spec(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
 #ifdef RT_DIAG
     if (env_int("RT_DEBUG_TIMES", 0) != 0) {  // diagnostic builds only (rt_debug_spec_times)
         const size_t n = size_t(P) * S * 2 * sizeof(uint32_t);
-        if (s->sp_dbg_t.bytes < n) {
-            s->sp_dbg_t.~DevBuf();
-            new (&s->sp_dbg_t) DevBuf();
-            HIP_OK(s->sp_dbg_t.alloc(n));
-        }
+        HIP_OK(s->sp_dbg_t.reserve(n));
         HIP_OK(hipMemsetAsync(s->sp_dbg_t.p, 0, n, st));
         R.dbg_start = s->sp_dbg_t.as<uint32_t>();
         R.dbg_end = R.dbg_start + size_t(P) * S;
@@ -1312,16 +1305,9 @@ int set_beam(rt_dev_scene *s, const rtk::Frame &f, rtk::InwScene &sc) {
     size_t free_b = 0, total_b = 0;
     const size_t grow = (s->inw_beam.bytes < need ? need : 0) + (s->inw_beam_n.bytes < need_n ? need_n : 0);
     if (grow && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || grow > free_b / 2)) return RT_OK;
-    if (s->inw_beam.bytes < need) {
-        s->inw_beam.~DevBuf();
-        new (&s->inw_beam) DevBuf();
-        if (s->inw_beam.alloc(need) != hipSuccess) { (void)hipGetLastError(); s->inw_beam.bytes = 0; return RT_OK; }
-    }
-    if (s->inw_beam_n.bytes < need_n) {
-        s->inw_beam_n.~DevBuf();
-        new (&s->inw_beam_n) DevBuf();
-        if (s->inw_beam_n.alloc(need_n) != hipSuccess) { (void)hipGetLastError(); s->inw_beam_n.bytes = 0; return RT_OK; }
-    }
+    // (bytes = 0 after a failure: `grow` above counts the buffer again next frame)
+    if (s->inw_beam.reserve(need) != hipSuccess) { (void)hipGetLastError(); s->inw_beam.bytes = 0; return RT_OK; }
+    if (s->inw_beam_n.reserve(need_n) != hipSuccess) { (void)hipGetLastError(); s->inw_beam_n.bytes = 0; return RT_OK; }
     sc.beam = s->inw_beam.as<uint2>();
     sc.beam_n = s->inw_beam_n.as<uint32_t>();
     sc.beam_cut = reinterpret_cast<const float *>(s->inw_beam_n.as<uint32_t>() + size_t(units) * nb);
@@ -1364,10 +1350,8 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     const uint32_t ring_sm = lring_sm ? rtk::kPmLdsRing : uint32_t(o.inw_ring_sm ? o.inw_ring_sm : 256);
     const size_t waves = std::max(size_t(blocks) * (rtk::kBlock / 64), size_t(blocks_ln) * (3 * rtk::kBlock / 64));
     const size_t ring_bytes = waves * std::max(lring ? 0u : ring_pm, lring_sm ? 0u : ring_sm) * sizeof(float4);
-    if (s->inw_ring.bytes < ring_bytes) {
-        s->inw_ring.~DevBuf();
-        new (&s->inw_ring) DevBuf();
-        if (s->inw_ring.alloc(ring_bytes) != hipSuccess) return RT_E_HIP;
+    if (!s->inw_ring.p || s->inw_ring.bytes < ring_bytes) {
+        if (s->inw_ring.reserve(ring_bytes) != hipSuccess) return RT_E_HIP;
         s->ring_frame = 0;  // fresh memory: clear it before the first frame
     }
     // ring tags carry the frame's epoch (rtk::ring_tag); the rings are cleared only when it wraps.
@@ -1384,15 +1368,8 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     sc.lring_sm = lring_sm ? 1u : 0u;
     sc.xcdq = o.inw_claim_xcd ? 1u : 0u;
 #ifdef RT_INW_PARK  // walk parking (experiment): 2 float4 per lane of the fold grid
-    {
-        const size_t need = waves * 64 * 2 * sizeof(float4);
-        if (s->inw_park.bytes < need) {
-            s->inw_park.~DevBuf();
-            new (&s->inw_park) DevBuf();
-            if (s->inw_park.alloc(need) != hipSuccess) return RT_E_HIP;
-        }
-        sc.park = s->inw_park.as<float4>();
-    }
+    if (s->inw_park.reserve(waves * 64 * 2 * sizeof(float4)) != hipSuccess) return RT_E_HIP;
+    sc.park = s->inw_park.as<float4>();
 #endif
     // the fused cull (cull4nf<true>: one fma per plane) while every ray origin -- the camera (+ lens and the unit step
     // of the primary ray), hit points inside the scene's boxes -- lies within 1000 of the origin
@@ -1408,12 +1385,8 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     if (o.inw_qnodes && s->layout != 4 && lring && sc.fused && sc.wnodes && s->qnodes.p) {
         const uint32_t gb = uint32_t(s->cus * rtk::resident_blocks_per_cu(19));
         const size_t need = size_t(gb) * rtk::kGqSub * rtk::kBlock * (rtk::kFStack / 4) * sizeof(float4);
-        if (s->gstk.bytes < need) {
-            s->gstk.~DevBuf();
-            new (&s->gstk) DevBuf();
-            if (s->gstk.alloc(need) != hipSuccess) { s->gstk.bytes = 0; return RT_E_HIP; }
-        }
-        if (rtk::kGqQn) sc.qnodes = s->qnodes.as<float4>();
+        if (s->gstk.reserve(need) != hipSuccess) return RT_E_HIP;
+        sc.qnodes = s->qnodes.as<float4>();
         sc.gstk = s->gstk.as<float4>();
         sc.gq_blocks = gb;
     }
@@ -1447,11 +1420,7 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     uint32_t *cost = nullptr;
     if (o.inw_claim_order) {
         const size_t need = (2 * size_t(rtk::units_of(f) / 64) + 256) * sizeof(uint32_t);
-        if (s->inw_cost.bytes < need) {
-            s->inw_cost.~DevBuf();
-            new (&s->inw_cost) DevBuf();
-            if (s->inw_cost.alloc(need) != hipSuccess) return RT_E_HIP;
-        }
+        if (s->inw_cost.reserve(need) != hipSuccess) return RT_E_HIP;
         cost = s->inw_cost.as<uint32_t>();
     }
     if (int rc = set_beam(s, f, sc); rc != RT_OK) return rc;
@@ -1473,8 +1442,7 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
         P.qnodes = sc.qnodes != nullptr;
         P.global_stack = sc.gstk != nullptr;
         P.walk_stack = sc.gstk ? rtk::kWStack : rtk::kFStack - 3;
-        if (sc.gstk)
-            P.lds_nodes = int(std::min<uint32_t>(s->n_wtree0, uint32_t(rtk::kGqQn ? rtk::kQLdsNodes : rtk::kInwLdsNodes)));
+        if (sc.gstk) P.lds_nodes = int(std::min<uint32_t>(s->n_wtree0, uint32_t(rtk::kQLdsNodes)));
         P.time_bins = sc.wnodes && !sc.gstk ? int(sc.wbins) : 0;  // the GQ walks read the staged (swept) tree
         P.beam_bins = sc.beam ? int(sc.beam_bins) : 0;
         P.sphere_records = sc.sph ? 1 : 0;

@@ -226,32 +226,11 @@ __device__ __forceinline__ float cull_t(float lx, float ly, float lz, float hx, 
 // stay scalar.  Same operations and rounding per plane as cull_t.
 typedef float pf2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ pf2 pk(float a, float b) { return pf2{a, b}; }
-__device__ __forceinline__ void cull4(const float4 lx, const float4 ly, const float4 lz, const float4 hx,
-                                      const float4 hy, const float4 hz, f3 o, f3 id, float lim, float &t0,
-                                      float &t1, float &t2, float &t3) {
-    const pf2 ox = pk(o.x, o.x), oy = pk(o.y, o.y), oz = pk(o.z, o.z);
-    const pf2 ix = pk(id.x, id.x), iy = pk(id.y, id.y), iz = pk(id.z, id.z);
-    const pf2 ax01 = (pk(lx.x, lx.y) - ox) * ix, bx01 = (pk(hx.x, hx.y) - ox) * ix;
-    const pf2 ay01 = (pk(ly.x, ly.y) - oy) * iy, by01 = (pk(hy.x, hy.y) - oy) * iy;
-    const pf2 az01 = (pk(lz.x, lz.y) - oz) * iz, bz01 = (pk(hz.x, hz.y) - oz) * iz;
-    const pf2 ax23 = (pk(lx.z, lx.w) - ox) * ix, bx23 = (pk(hx.z, hx.w) - ox) * ix;
-    const pf2 ay23 = (pk(ly.z, ly.w) - oy) * iy, by23 = (pk(hy.z, hy.w) - oy) * iy;
-    const pf2 az23 = (pk(lz.z, lz.w) - oz) * iz, bz23 = (pk(hz.z, hz.w) - oz) * iz;
-    auto one = [&](float x0, float x1, float y0, float y1, float z0, float z1) {
-        const float te = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
-        const float tx = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
-        return (te <= tx && tx >= -1e-3f && te <= lim) ? te : kMiss;
-    };
-    t0 = one(ax01.x, bx01.x, ay01.x, by01.x, az01.x, bz01.x);
-    t1 = one(ax01.y, bx01.y, ay01.y, by01.y, az01.y, bz01.y);
-    t2 = one(ax23.x, bx23.x, ay23.x, by23.x, az23.x, bz23.x);
-    t3 = one(ax23.y, bx23.y, ay23.y, by23.y, az23.y, bz23.y);
-}
-// The same test with the planes already split into near and far by the ray's octant (the caller
+// The planes arrive already split into near and far by the ray's octant (the caller
 // loads plane a + 3 s_a as near and a + 3 (1 - s_a) as far, s_a = 1 when d_a < 0).  With a finite,
 // nonzero reciprocal the slab value (p - o) * (1/d) is monotone in p, so the near plane's value is
-// the min of the pair and the far plane's the max: te and tx have cull4's bits and the 12 min / max
-// per node are gone.  A zero component (1/d = inf) keeps at least the boxes cull4 keeps: the pair
+// the min of the pair and the far plane's the max: te and tx have cull_t's bits and the 12 min / max
+// per node are gone.  A zero component (1/d = inf) keeps at least the boxes cull_t keeps: the pair
 // form's fminf / fmaxf drop a NaN (origin on a plane) and then cull, the octant form keeps the box.
 // The culling BVH only decides which objects get the exact test (iow_launch_ray), so that is exact.
 __device__ __forceinline__ void cull4o(const float4 nx, const float4 ny, const float4 nz, const float4 fx,
@@ -373,19 +352,10 @@ __device__ __forceinline__ RayRet iow_eval(const IowScene &S, f3 go, f3 gd, f3 t
 }
 
 // IOW BVH-stack slot p of a lane (16-bit links), [slot][lane]: two lanes share a dword, so two
-// lanes of an LDS access group whose stack depths differ hit one bank (a 2-way conflict).
-// RT_IOW_BSTK_PAIR (A/B variant, round 5): [slot pair][lane][2], the lane's two slots in its own
-// dword, conflict-free at any depths: C2's LDS bank-conflict cycles fell from 17.5% to 13.0% of the
-// LDS-active cycles, and the frame took 3.8% longer (3,835 / 3,857 against 3,702 / 3,699 ms, same
-// box, profiles/r05_ab_stackless_iow_bstk.json): the address arithmetic of every push and pop costs more
-// than the conflicts did.  b = the lane's base, lds + kBstkLane * lane.
-#ifdef RT_IOW_BSTK_PAIR
-__device__ __forceinline__ short &bslot(short *b, int p) { return b[(p >> 1) * (2 * kBlock) + (p & 1)]; }
-constexpr int kBstkLane = 2;
-#else
+// lanes of an LDS access group whose stack depths differ hit one bank (a 2-way conflict).  The
+// conflict-free pair layout cost more in address arithmetic than the conflicts did
+// (DESIGN_HISTORY.md §J).  b = the lane's base, lds + lane.
 __device__ __forceinline__ short &bslot(short *b, int p) { return b[p * kBlock]; }
-constexpr int kBstkLane = 1;
-#endif
 
 // LaunchRay 03...glsl:196-256.  The reference loops over every object and keeps the first
 // strictly nearer hit, i.e. the minimum t with the lowest index among exact ties.  The BVH
@@ -421,11 +391,9 @@ __device__ RayRet iow_launch_ray(const IowScene &S, const Frame &F_, f3 go, f3 g
         // children), tests the four boxes, enters the nearest hit child and pushes the others
         // farthest-first.
         DBG_T0(F_, t_trav);
-#ifndef RT_IOW_NO_OCTANT
         // the ray's near / far plane of each axis (cull4o): low planes are float4 0-2, high 3-5
         const int nxo = gd.x < 0.0f ? 3 : 0, nyo = gd.y < 0.0f ? 4 : 1, nzo = gd.z < 0.0f ? 5 : 2;
         const int fxo = 3 - nxo, fyo = 5 - nyo, fzo = 7 - nzo;
-#endif
         int sp = 0, pend = -1, cur = S.root_link;
         bool walking = true, ovf = false;  // ovf: a child was dropped by a full stack
         float lim = min_t * 1.0001f + 1e-3f;  // culling limit, follows min_t
@@ -438,12 +406,7 @@ __device__ RayRet iow_launch_ray(const IowScene &S, const Frame &F_, f3 go, f3 g
                     const float4 lk = nd[6];  // child links as int bits (set_iow_bvh)
                     c.nodes += 4;
                     float t0, t1, t2, t3;
-#ifndef RT_IOW_NO_OCTANT
                     cull4o(nd[nxo], nd[nyo], nd[nzo], nd[fxo], nd[fyo], nd[fzo], go, id, lim, t0, t1, t2, t3);
-#else
-                    const float4 lx = nd[0], ly = nd[1], lz = nd[2], hx = nd[3], hy = nd[4], hz = nd[5];
-                    cull4(lx, ly, lz, hx, hy, hz, go, id, lim, t0, t1, t2, t3);
-#endif
                     int k0 = __float_as_int(lk.x), k1 = __float_as_int(lk.y), k2 = __float_as_int(lk.z),
                         k3 = __float_as_int(lk.w);
                     // sort (t, link) ascending; misses carry t = +inf
@@ -564,7 +527,7 @@ __device__ void iow_coop_search(const IowScene &S, f3 go, f3 gd, float max_t, sh
                     const unsigned long long cm = __ballot(cand);
                     if (cand) {
                         const uint32_t k = cnt + lanes_below(cm);
-                        bslot(wl + kBstkLane * (k & 63), (int)(k >> 6)) = (short)j;
+                        bslot(wl + (k & 63), (int)(k >> 6)) = (short)j;
                     }
                     cnt += (uint32_t)__popcll(cm);
                 }
@@ -579,7 +542,7 @@ __device__ void iow_coop_search(const IowScene &S, f3 go, f3 gd, float max_t, sh
         for (uint32_t k0 = 0; k0 < cnt; k0 += 64) {
             const uint32_t k = k0 + lane;
             if (k < cnt) {
-                const int j = cull ? (int)bslot(wl + kBstkLane * (k & 63), (int)(k >> 6)) : (int)(jb + k);
+                const int j = cull ? (int)bslot(wl + (k & 63), (int)(k >> 6)) : (int)(jb + k);
                 const float4 *cold = reinterpret_cast<const float4 *>(S.cold + (size_t)j * kIowCold);
                 const float4 q0 = cold[0], q1 = cold[1];
                 const int was = bj;
@@ -749,7 +712,7 @@ __device__ __forceinline__ void iow_seg_step(const IowScene &S, const Frame &F, 
         return;
     }
     constexpr int kCap = BS * 64;  // the wave's BVH-stack slots, as a list
-    short *wl = bstk - kBstkLane * (threadIdx.x & 63);
+    short *wl = bstk - (threadIdx.x & 63);
     DBG_T0(F, t_pop);
     SegIn in{};
     if (seg) in = iow_seg_pop(S, K, sidx);
@@ -903,7 +866,7 @@ __device__ __forceinline__ void iow03_body(const Frame &f, const IowScene &S, co
     __shared__ unsigned long long s_dbg[SUB * kBlock / 64][kDbgSlots];
     __shared__ float4 s_nodes[LN ? kIowLdsNodes * 7 : 1];
     const int sb = (int)(threadIdx.x / kBlock), tl = (int)(threadIdx.x % kBlock);
-    short *bstk = lds_bvh + sb * Cfg::BS * kBlock + kBstkLane * tl;  // bslot's layout
+    short *bstk = lds_bvh + sb * Cfg::BS * kBlock + tl;  // bslot's layout
     const float4 *nodes = iow_stage_nodes<LN>(S, s_nodes);
     Ctr c;
     if (f.dbg) {
@@ -1128,7 +1091,7 @@ __device__ __forceinline__ void iow03s_body(const Frame &f, const IowScene &S, c
     __shared__ unsigned long long s_dbg[SUB * kBlock / 64][kDbgSlots];
     __shared__ float4 s_nodes[LN ? kIowLdsNodes * 7 : 1];
     const int sb = (int)(threadIdx.x / kBlock), tl = (int)(threadIdx.x % kBlock);
-    short *bstk = lds_bvh + sb * Cfg::BS * kBlock + kBstkLane * tl;  // bslot's layout
+    short *bstk = lds_bvh + sb * Cfg::BS * kBlock + tl;  // bslot's layout
     const float4 *nodes = iow_stage_nodes<LN>(S, s_nodes);
     Ctr c;  // per unit here: written to the unit's record, never flushed
     if (f.dbg) {
@@ -1962,7 +1925,7 @@ __device__ float inw_surrounding_ri(const InwScene &S, KS &K, f3 hp, float ratio
 // there; deeper nodes come from global memory.
 // INW wide node: 10 float4, SoA over the 4 children: planes lx ly lz hx hy hz, then lx ly lz again,
 // then the child links.  The repeat lets a ray read its near and far planes of axis a at
-// a + 3*s_a and a + 3 + 3*s_a (s_a = 1 when d_a < 0): one per-lane offset per axis (inw_wnode_nf).
+// a + 3*s_a and a + 3 + 3*s_a (s_a = 1 when d_a < 0): one per-lane offset per axis (inw_wnode_nf_buf).
 constexpr int kInwNodeF4 = 10;
 // 236 nodes (36.9 KB): what the 3 x 256-lane stacks (120 KB) and k_inw_pm's depth slots (3 KB)
 // leave of 160 KB
@@ -1986,29 +1949,11 @@ __device__ __forceinline__ void inw_wnode(const InwScene &S, int cur, float4 &lx
     const float4 *nd = inw_node_ptr<LN>(S, cur);
     lx = nd[0]; ly = nd[1]; lz = nd[2]; hx = nd[3]; hy = nd[4]; hz = nd[5]; lk = nd[9];
 }
-// The near and far planes of the four children for this ray's octant (oa = a + 3*s_a).
-template <bool LN>
-__device__ __forceinline__ void inw_wnode_nf(const InwScene &S, int cur, uint32_t ox, uint32_t oy, uint32_t oz,
-                                             float4 &nx, float4 &ny, float4 &nz, float4 &fx, float4 &fy, float4 &fz,
-                                             float4 &lk) {
-#ifndef RT_INW_FLAT
-    if (LN && (uint32_t)(cur - 1) < S.n_lnodes) {  // ds_read_b128 (a generic pointer would make flat loads)
-        const float4 *nd = g_inw_lnodes + kInwNodeF4 * (cur - 1);
-        const float4 *px = nd + ox, *py = nd + oy, *pz = nd + oz;
-        nx = px[0]; fx = px[3]; ny = py[0]; fy = py[3]; nz = pz[0]; fz = pz[3]; lk = nd[9];
-        return;
-    }
-    const float4 *nd = S.wnodes + kInwNodeF4 * (cur - 1);
-#else
-    const float4 *nd = inw_node_ptr<LN>(S, cur);
-#endif
-    const float4 *px = nd + ox, *py = nd + oy, *pz = nd + oz;
-    nx = px[0]; fx = px[3]; ny = py[0]; fy = py[3]; nz = pz[0]; fz = pz[3]; lk = nd[9];
-}
-// The same fetch from global memory as buffer loads: the node's byte offset is 32 bits (a node
+// The near and far planes of the four children for this ray's octant (oa = a + 3*s_a), fetched
+// from global memory as buffer loads: the node's byte offset is 32 bits (a node
 // index times 160), the octant offsets and the far planes' +48 / the links' +144 fold into the
 // instructions, so a node step spends 4 VALU on addresses instead of the 64-bit pointer sums (~10)
-// (C3 185.9 -> 184.2 ms on one box, profiles/r06_ab2_gq.json; -DRT_INW_NO_BUFLOAD: the pointer form)
+// (C3 185.9 -> 184.2 ms on one box, profiles/r06_ab_gq_waves.json)
 __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
     return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
@@ -2037,7 +1982,7 @@ template <bool LN>
 __device__ __forceinline__ void inw_wnode_nf_buf(const InwScene &S, const WnodeBuf &W, int cur, uint32_t oxb,
                                                  uint32_t oyb, uint32_t ozb, float4 &nx, float4 &ny, float4 &nz,
                                                  float4 &fx, float4 &fy, float4 &fz, float4 &lk) {
-    if (LN && (uint32_t)(cur - 1) < S.n_lnodes) {
+    if (LN && (uint32_t)(cur - 1) < S.n_lnodes) {  // ds_read_b128 (a generic pointer would make flat loads)
         const float4 *nd = g_inw_lnodes + kInwNodeF4 * (cur - 1);
         const float4 *px = nd + (oxb >> 4), *py = nd + (oyb >> 4), *pz = nd + (ozb >> 4);
         nx = px[0]; fx = px[3]; ny = py[0]; fy = py[3]; nz = pz[0]; fz = pz[3]; lk = nd[9];
@@ -2143,9 +2088,7 @@ __device__ __forceinline__ void cull4q(const float4 a, const float4 b, const flo
 // loads) before the caller's box-test branch, instead of sinking the loads behind the branch --
 // one round trip for box and record instead of two or three (leaf tests, beam candidates)
 __device__ __forceinline__ void keep_before_branch(f3 to, f3 td) {
-#ifndef RT_LEAF_SINK
     asm volatile("" ::"v"(to.x), "v"(to.y), "v"(to.z), "v"(td.x), "v"(td.y), "v"(td.z));
-#endif
 }
 
 // Scalar loads of wave-uniform records (constant address space: s_load through the scalar cache,
@@ -2189,10 +2132,9 @@ __device__ __forceinline__ float4 sload4(const float4 *p, int i) {
 #define RT_INW_PARK_MIN 4
 #endif
 constexpr int kParkLanes = RT_INW_PARK_LANES, kParkMinTrips = RT_INW_PARK_MIN;
-#ifndef RT_INW_LEAF_BATCH
-#define RT_INW_LEAF_BATCH 65
-#endif
-constexpr int kInwLeafBatch = RT_INW_LEAF_BATCH;
+// Postponed leaves are tested once every walking lane holds one; a smaller batch (once this many
+// lanes hold one) was an experiment, and 65 = more than a wave = off
+constexpr int kInwLeafBatch = 65;
 struct WalkPark {
     float4 *slot;   // this lane's 2 float4
     bool resume;    // the walk was parked in an earlier iteration: restore it
@@ -2206,7 +2148,6 @@ struct WalkPark {
 template <bool SP>
 __device__ __forceinline__ void inw_hit_normal(const InwScene &S, int bg, f3 o, f3 d, float ratio, float bt, f3 &normal,
                                                float &extra) {
-#ifndef RT_INW_SPH_NO_NORMAL
     if (SP && S.sph) {
         const float4 p = S.sph[3 * bg], q = S.sph[3 * bg + 1], w = S.sph[3 * bg + 2];
         const f3 ov = (o - mk(p.x, p.y, p.z)) + mk(q.x, q.y, q.z) * (1.0f - ratio);
@@ -2217,10 +2158,8 @@ __device__ __forceinline__ void inw_hit_normal(const InwScene &S, int bg, f3 o, 
         extra = w.w;
         return;
     }
-#endif
     const Xf x = load_xf(S, bg);
     f3 ov = (o - x.pos) + x.delta * (1.0f - ratio);
-#ifndef RT_INW_NO_IDENT
     if (x.ident) {  // R = I: h = ov + d bt has the same floats (d has no zero component here), and
                     // mul(I, nl) with the literal identity repeats the loaded R's operations
         const f3 h = ov + d * bt;
@@ -2233,7 +2172,6 @@ __device__ __forceinline__ void inw_hit_normal(const InwScene &S, int bg, f3 o, 
         extra = x.extra;
         return;
     }
-#endif
     f3 to = tmul(x.R, ov), td = tmul(x.R, d);
     f3 h = to + td * bt, nl;
     if (x.type == 1) nl = normalize(f3{h.x * x.is2.x, h.y * x.is2.y, h.z * x.is2.z});
@@ -2271,9 +2209,7 @@ __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float r
     int cap;
     float *const wsb = K.walk_stack(PK ? 8u : 0u, 3, cap);  // entry p at wsb[p * kBlock]
     const uint32_t ox = d.x < 0.0f ? 3u : 0u, oy = d.y < 0.0f ? 4u : 1u, oz = d.z < 0.0f ? 5u : 2u;
-#ifndef RT_INW_NO_BUFLOAD
     const WnodeBuf wrs = wnode_buf(S, ox * 16u, oy * 16u, oz * 16u);
-#endif
     int sp = 0, pend = -1, cur = S.wroot;
     if (!LN && S.wbins > 1u) {  // the ray's time-bin tree (the staged nodes are the swept tree's)
         const int b = min((int)(ratio * (float)S.wbins), (int)S.wbins - 1);
@@ -2308,16 +2244,13 @@ __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float r
             const Xf x = load_xf(S, g);  // loaded with the box, before its test: one memory latency
             const bool inb = test_aabb_te(n0, n1, o, id, tlim0, te);
             const f3 ov = (o - x.pos) + x.delta * (1.0f - ratio);
-#ifndef RT_INW_NO_IDENT
             if (x.ident) {  // R = I: tmul(R, v) is v (up to zero signs, which t cannot see; d has no
                             // zero component here), and rcp(d) is the ray's own id
                 keep_before_branch(ov, d);
                 if (!inb) return;
                 if (x.type == 1) t = t_ellipsoid(ov, d, x.is);
                 else if (x.type == 2) t = t_cuboid_rcp(ov, id, x.scale);
-            } else
-#endif
-            {
+            } else {
                 f3 to = tmul(x.R, ov), td = tmul(x.R, d);
                 keep_before_branch(to, td);
                 if (!inb) return;
@@ -2327,9 +2260,6 @@ __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float r
         }
         if (t > 0.0f && t < tlim0) {
             const uint32_t r = rank[g];
-#ifdef RT_INW_GUARD_ANY
-            if (t < te) ovf = true;  // round-5 guard: any hit below its leaf-box entry
-#endif
             if (t < bt || (t == bt && r < br)) {
                 if (bg >= 0) t2 = fminf(t2, bt);
                 bt = t; bg = g; br = r; bte = te; lim = bt * 1.0001f + 1e-3f;
@@ -2363,25 +2293,7 @@ __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float r
                     cull4q(qa, qb, qc, ox != 0u, oy != 1u, oz != 2u, fid, noid, lim, t0, t1, t2, t3);
                 } else {
                     float4 nx, ny, nz, fx, fy, fz;
-#ifndef RT_INW_NO_BUFLOAD
-#ifdef RT_INW_NODE_SLOAD
-                    // every stepping lane at one node with one octant (30% of C3's node steps are at one
-                    // node): the node's planes by scalar loads, off the TA path
-                    const int c0 = __builtin_amdgcn_readfirstlane(cur);
-                    const uint32_t oc = ox + 8u * oy + 64u * oz, oc0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)oc);
-                    if (S.cnodes && (!LN || (uint32_t)(c0 - 1) >= S.n_lnodes) && __ballot(cur != c0 || oc != oc0) == 0ull) {
-                        const float4 *nd = S.cnodes + 7 * (c0 - 1);
-                        const int sx = (int)(oc0 & 7u), sy = (int)((oc0 >> 3) & 7u), sz = (int)(oc0 >> 6);  // 0|3, 1|4, 2|5
-                        nx = sload4(nd, sx); fx = sload4(nd, 3 - sx);
-                        ny = sload4(nd, sy); fy = sload4(nd, 5 - sy);
-                        nz = sload4(nd, sz); fz = sload4(nd, 7 - sz);
-                        lk = sload4(nd, 6);
-                    } else
-#endif
                     inw_wnode_nf_buf<LN>(S, wrs, cur, ox * 16u, oy * 16u, oz * 16u, nx, ny, nz, fx, fy, fz, lk);
-#else
-                    inw_wnode_nf<LN>(S, cur, ox, oy, oz, nx, ny, nz, fx, fy, fz, lk);
-#endif
                     cull4nf<FU>(nx, ny, nz, fx, fy, fz, o, fid, noid, lim, t0, t1, t2, t3);
                 }
                 c.nodes += 4;
@@ -2408,8 +2320,7 @@ __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float r
             }
             if (ovf) walking = false;
         }
-        // postponed leaves are tested once every walking lane holds one (RT_INW_LEAF_BATCH < 65: or
-        // once that many lanes hold one, an experiment)
+        // postponed leaves are tested once every walking lane holds one (or kInwLeafBatch lanes)
         if (__all(!walking || pend >= 0) ||
             (kInwLeafBatch < 65 && __popcll(__ballot(pend >= 0)) >= (unsigned)kInwLeafBatch)) {
             OCC_TALLY(c, kOccLeaf, pend >= 0);
@@ -2520,16 +2431,11 @@ __device__ float inw_closest_beam(const InwScene &S, const KS &K, f3 o, f3 d, fl
             float4 n0, n1;
             float te, t = -1.0f;
             bool inb;
-#ifndef RT_INW_BEAM_VLOAD
             // one candidate for every active lane (a wave's lanes trace samples of one pixel and step
             // through its list together): scalar loads, C3 184.7 -> 182.5 ms
-            // (profiles/r06_ab_beam_sload_ring_il.json; -DRT_INW_BEAM_VLOAD: vector loads only)
+            // (profiles/r06_ab_beam_sload_ring_il.json)
             const int g0 = __builtin_amdgcn_readfirstlane(g);
             const bool uni_g = __ballot(g != g0) == 0ull;
-#else
-            const int g0 = g;
-            const bool uni_g = false;
-#endif
             if (S.sph) {  // a sphere scene (inw_traverse_wide's leaf test): 2 float4, R = I
                 float4 p, q;
                 if (uni_g) {
@@ -2564,9 +2470,6 @@ __device__ float inw_closest_beam(const InwScene &S, const KS &K, f3 o, f3 d, fl
             if (inb) {
                 if (t > 0.0f && t < tlim0) {
                     const uint32_t r = rank[g];
-#ifdef RT_INW_GUARD_ANY
-                    if (t < te) ovf = true;
-#endif
                     if (t < bt || (t == bt && r < br)) {  // the leaf-entry guard as in inw_traverse_wide
                         if (bg >= 0) t2 = fminf(t2, bt);
                         bt = t; bg = g; br = r; bte = te; lim = bt * kap * 1.00001f + 0.01f;
@@ -3237,12 +3140,8 @@ __global__ __launch_bounds__(kBlock) void k_inw(Frame f, InwScene S, Chunk ch, C
 // ---------------------------------------------------------------- INW wave counts
 // Waves per SIMD of the 256-lane INW kernels: INW-04 (LIGHTS) at 3 (159 VGPRs, no spills);
 // INW-01 at 4 (128 VGPRs with a few spills, 8% faster on C3 than 3 waves in round 2).
-#ifndef RT_INW_WAVES
-#define RT_INW_WAVES 3
-#endif
-#ifndef RT_INW01_WAVES
-#define RT_INW01_WAVES 4  // INW-01: 128 VGPRs with a few spills, 8% faster on C3 than 3 waves
-#endif
+constexpr int kInwWaves = 3;
+constexpr int kInw01Waves = 4;  // INW-01: 128 VGPRs with a few spills, 8% faster on C3 than 3 waves
 
 // ---------------------------------------------------------------- INW: on-chip End() folds
 // End() (01_BVH...glsl:625-653, 664-675) adds each sample's sqrt(colour) in sample order and
@@ -3517,42 +3416,21 @@ __global__ __launch_bounds__(kBlock) void k_inw_order_scatter(const uint32_t *ke
 // GQ (DESIGN.md §5.1 "GQ"; LN, FU, LRING and INW-01 only): the reference's 40-float stacks in
 // global memory (GStack, S.gstk), the wide walks' node stacks in LDS (kWStack entries per lane), the
 // closest-hit walks over the quantised nodes, the top kQLdsNodes of them staged in LDS
-#ifndef RT_GQ_STAGE
-#define RT_GQ_STAGE 1
-#endif
 // k_inw_pm's LDS fold ring: channel c of entry e.  Planes (r, g, b of 256 entries each): the fold's
 // lanes 0, 1, 2 read one plane each at the same entry, addresses 1 KB apart, one bank: a 3-way
-// conflict per read.  RT_RING_IL interleaves the channels (3 e + c): the three lanes hit 3 banks,
-// but C3 ran 0.5% slower (185.7 against 184.7 ms, profiles/r06_ab_beam_sload_ring_il.json).
-#ifdef RT_RING_IL
-#define RIX(c, e) (3u * (e) + (c))
-#else
+// conflict per read.  Interleaving the channels (3 e + c) spreads them over 3 banks, but C3 ran 0.5%
+// slower (DESIGN_HISTORY.md §J).
 #define RIX(c, e) ((c) * kPmLdsRing + (e))
-#endif
-#ifndef RT_INW_R1_MIN
-#define RT_INW_R1_MIN 0
-#endif
-constexpr int kR1Min = RT_INW_R1_MIN;  // k_inw_pm: round 1 waits for this many lanes with a ray (0 = off)
-#ifdef RT_GQ_FSTACK
-constexpr bool kGqGlobalStack = false;
-#else
-constexpr bool kGqGlobalStack = true;
-#endif
-constexpr bool kGqStage = RT_GQ_STAGE != 0;
-static_assert(kGqLdsFree >= kInwLdsNodes * kInwNodeF4 * 16, "GQ: room for the 236 full nodes");
 template <bool LN, bool GQ>
-constexpr int pm_sub() { return GQ && kGqGlobalStack ? kGqSub : (LN ? 3 : 1); }
+constexpr int pm_sub() { return GQ ? kGqSub : (LN ? 3 : 1); }
 template <bool LIGHTS, bool LN = false, bool FU = false, bool LRING = false, bool GQ = false>
-__global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_waves_per_eu((LN ? pm_sub<LN, GQ>() : (LIGHTS ? RT_INW_WAVES : RT_INW01_WAVES))))) void k_inw_pm(Frame f, InwScene S0, float4 *ring, uint32_t rmask, unsigned *counter, const uint32_t *mode, uint32_t force, const uint32_t *border) {
+__global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_waves_per_eu((LN ? pm_sub<LN, GQ>() : (LIGHTS ? kInwWaves : kInw01Waves))))) void k_inw_pm(Frame f, InwScene S0, float4 *ring, uint32_t rmask, unsigned *counter, const uint32_t *mode, uint32_t force, const uint32_t *border) {
     static_assert(!GQ || (LN && FU && LRING && !LIGHTS), "GQ: the C3 instance only");
     if (inw_sample_major(mode, force)) return;  // the probe picked k_inw_sm for this frame
     constexpr int SUB = pm_sub<LN, GQ>();
-    // GS: the global 40-float stacks (GQ; the RT_GQ_FSTACK experiment keeps FStack), GST: the top
-    // of the culling BVH staged in the LDS that frees (RT_GQ_STAGE=0: none, an experiment), QN:
-    // quantised nodes (else the full ones, 236 in g_inw_lnodes)
-    constexpr bool GS = GQ && kGqGlobalStack, GST = GS && kGqStage, QN = GQ && kGqQn;
-    // FStack instances: the three 256-lane 40-float stacks; GS: the wide walks' node stacks
-    __shared__ float lds[SUB * (GS ? kWStack : kFStack) * kBlock];
+    // FStack instances: the three 256-lane 40-float stacks; GQ: the wide walks' node stacks (the
+    // 40-float stacks are global), the LDS that frees holding the top of the quantised culling BVH
+    __shared__ float lds[SUB * (GQ ? kWStack : kFStack) * kBlock];
     // per wave: the middle sample's depth of claimed ordinal j (slot j % 64; at most 64 ordinals lie
     // between the fold and the issue), written out with the pixel's colour
     __shared__ float s_pdep[SUB * kBlock];
@@ -3564,22 +3442,15 @@ __global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_
     // ring leaves room for sit in L1 anyway, and the walk loop without the LDS branch (its exec
     // masking and the base pointer kept in a VGPR lane) ran C3 2% faster.  GQ
     // stages kQLdsNodes quantised nodes beside its ring
-    constexpr bool WLN = LN && (!LR || GST);
+    constexpr bool WLN = LN && (!LR || GQ);
     float *lr;  // LR: this wave's ring, three planes (r, g, b) of kPmLdsRing floats
-    if constexpr (GS) {
+    if constexpr (GQ) {
         __shared__ float s_ring[SUB * kBlock / 64 * 3 * kPmLdsRing];
         lr = s_ring + uni((threadIdx.x >> 6) * (3u * kPmLdsRing));
-        if constexpr (GST && QN) {
-            const uint32_t n = S.qnodes ? (S.n_wnodes < (uint32_t)kQLdsNodes ? S.n_wnodes : (uint32_t)kQLdsNodes) : 0u;
-            for (uint32_t i = threadIdx.x; i < n * (uint32_t)kQNodeF4; i += SUB * kBlock) g_inw_qlds[i] = S.qnodes[i];
-            __syncthreads();
-            S.n_lnodes = n;
-        } else if constexpr (GST) {
-            const uint32_t n = S.wnodes ? (S.n_wnodes < (uint32_t)kInwLdsNodes ? S.n_wnodes : (uint32_t)kInwLdsNodes) : 0u;
-            for (uint32_t i = threadIdx.x; i < n * (uint32_t)kInwNodeF4; i += SUB * kBlock) g_inw_lnodes[i] = S.wnodes[i];
-            __syncthreads();
-            S.n_lnodes = n;
-        }
+        const uint32_t n = S.qnodes ? (S.n_wnodes < (uint32_t)kQLdsNodes ? S.n_wnodes : (uint32_t)kQLdsNodes) : 0u;
+        for (uint32_t i = threadIdx.x; i < n * (uint32_t)kQNodeF4; i += SUB * kBlock) g_inw_qlds[i] = S.qnodes[i];
+        __syncthreads();
+        S.n_lnodes = n;
     } else {
         lr = reinterpret_cast<float *>(g_inw_lnodes + kPmLdsNodes * kInwNodeF4) + uni((threadIdx.x >> 6) * (3u * kPmLdsRing));
         if constexpr (WLN) {
@@ -3599,9 +3470,9 @@ __global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_
     const unsigned long long t_start = wall_clock64();  // the tail split (tools/inw_split.py)
     unsigned long long t_qd = 0;
 #endif
-    using KS = std::conditional_t<GS, GStack, FStack>;
+    using KS = std::conditional_t<GQ, GStack, FStack>;
     KS K;
-    if constexpr (GS) {
+    if constexpr (GQ) {
         K.col = S.gstk + ((size_t)blockIdx.x * (SUB * kBlock) + threadIdx.x);
         K.stride = gridDim.x * (SUB * kBlock);
         K.ws = lds + (threadIdx.x / kBlock) * (kWStack * kBlock) + (threadIdx.x % kBlock);
@@ -3674,7 +3545,6 @@ __global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_
                 const unsigned long long m = __ballot(fin);
                 n = ~m == 0ull ? 64u : (uint32_t)__builtin_ctzll(~m);
             }
-#ifndef RT_FOLD_READLANE
             if constexpr (LR) {
                 // LDS ring: lanes 0, 1, 2 add the r, g, b planes' entries straight from LDS, each
                 // its channel in sample order (the same float additions, two instructions per entry
@@ -3716,7 +3586,6 @@ __global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_
                 gf += n;
                 continue_fold = false;
             }
-#endif
             // the run splits at pixel ends: per pixel, its entries are added with no test between them
             for (uint32_t i = 0; continue_fold && i < n;) {
                 const uint32_t e = i + (n - i < spp - sf ? n - i : spp - sf);
@@ -3862,7 +3731,7 @@ __global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_
             if (go) {
                 WalkPark wp{pslot, parked, false};
                 if (f.px_rays && !parked) atomicAdd(f.px_rays + px.out, 1u);  // rt_debug_pixel_rays (diagnostics only)
-                inw_segment<LIGHTS, WLN, FU, PK, QN>(S, f, K, s, col, dep, c, bu, &wp);
+                inw_segment<LIGHTS, WLN, FU, PK, GQ>(S, f, K, s, col, dep, c, bu, &wp);
                 parked = PK && wp.parked;
             }
 #ifdef RT_DIAG_SPLIT
@@ -3880,19 +3749,6 @@ __global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_
                 }
                 if ((uint32_t)s == mid) pdep[pj] = dep;  // 01_BVH...glsl:667-668, stored with the pixel's colour
                 busy = false;
-            }
-            // Bounce-walk fill: the wide walk of round 1 costs a wave the same
-            // trips however few of its lanes hold a bounce ray, and primary rays (beam lists) are
-            // cheap.  While fewer than kR1Min lanes hold a ray for round 1 and free lanes could take
-            // more samples, skip round 1: the next iteration issues samples to the free lanes and
-            // runs their primaries, and the bounce rays pile up for one fuller walk.  Every
-            // iteration issues at least one entry while that holds, so the loop always advances.
-            if (kR1Min > 0 && round == 0) {
-                const uint32_t nb = (uint32_t)__popcll(__ballot(busy && K.size > 0u));
-                const bool nfree = __ballot(!busy) != 0ull;
-                const bool more = nfree && (uint64_t)(nclaimed - ji) * spp - si + (qdone ? 0u : 1u) > 0u &&
-                                  gi - gf < rsize;
-                if (nb < (uint32_t)kR1Min && more) break;
             }
         }
         INW_CYC(c, 4, t_seg);
@@ -3929,7 +3785,7 @@ __global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_
 // LRING: the fold ring in LDS after the first kPmLdsNodes staged nodes, as k_inw_pm's (InwScene::
 // lring_sm: chosen when the scene's BVH top fits those nodes, so the staging loses nothing)
 template <bool LIGHTS, bool LN = false, bool FU = false, bool LRING = false>
-__global__ __launch_bounds__(LN ? 3 * kBlock : kBlock) __attribute__((amdgpu_waves_per_eu(LN ? 3 : (LIGHTS ? RT_INW_WAVES : RT_INW01_WAVES)))) void k_inw_sm(Frame f, InwScene S0, float4 *ring, uint32_t rmask, unsigned *counter, const uint32_t *mode, uint32_t force, const uint32_t *) {
+__global__ __launch_bounds__(LN ? 3 * kBlock : kBlock) __attribute__((amdgpu_waves_per_eu(LN ? 3 : (LIGHTS ? kInwWaves : kInw01Waves)))) void k_inw_sm(Frame f, InwScene S0, float4 *ring, uint32_t rmask, unsigned *counter, const uint32_t *mode, uint32_t force, const uint32_t *) {
     if (!inw_sample_major(mode, force)) return;  // the probe picked k_inw_pm for this frame
     constexpr int SUB = LN ? 3 : 1;
     constexpr bool LR = LN && LRING;

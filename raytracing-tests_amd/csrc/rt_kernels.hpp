@@ -253,18 +253,11 @@ constexpr uint32_t kPmLdsNodes = 5;      // ... and the nodes it leaves staged
 // kGqSub 256-lane sub-blocks per block (= waves per SIMD; 1 block per CU), per block the wide walks'
 // node stacks in LDS (kWStack entries per lane), the fold rings (3 KB per wave), the depth slots,
 // and in the rest of the CU's 160 KB the top of the culling BVH: kQLdsNodes quantised nodes
-// (kGqQn; 64 B each) or the 236 full ones of g_inw_lnodes
+// (64 B each)
 constexpr int kFStack = 40;  // stack_capacity (FLT_STACK, 01_BVH...glsl:80)
 constexpr int kWStack = 16;
 constexpr int kQNodeF4 = 4;
-#ifndef RT_GQ_SUB
-#define RT_GQ_SUB 3
-#endif
-#ifndef RT_GQ_QN
-#define RT_GQ_QN 1
-#endif
-constexpr int kGqSub = RT_GQ_SUB;
-constexpr bool kGqQn = RT_GQ_QN != 0;
+constexpr int kGqSub = 3;
 constexpr int kGqLdsFree = 163840 - kGqSub * kWStack * kBlock * 4 - kGqSub * 4 * 3 * (int)kPmLdsRing * 4 -
                            kGqSub * kBlock * 4;
 constexpr int kQLdsNodes = kGqLdsFree / 64;

@@ -1,4 +1,4 @@
-"""ctypes binding of librt_hip.so (include/rt_hip.h + include/rt_scene.h).
+"""ctypes binding of librt_hip.so (include/rt_hip.h + include/rt_hip_debug.h + include/rt_scene.h).
 
 This is the Python side of the drop-in boundary: a thin mirror of the C ABI with numpy
 arrays in and out.  It loads the in-tree HIP library and fails loudly if it is missing --
@@ -87,7 +87,7 @@ class RtOptions(C.Structure):
 
 
 class RtPathInfo(C.Structure):
-    """rt_path_info (include/rt_hip.h): what a scene's last render ran."""
+    """rt_path_info (include/rt_hip_debug.h): what a scene's last render ran."""
     _fields_ = [("kernel", C.c_char * 64), ("launches", C.c_int), ("order", C.c_int), ("order_forced", C.c_int),
                 ("wide_walk", C.c_int), ("beams", C.c_int), ("ri_grid", C.c_int), ("fused_cull", C.c_int),
                 ("lds_nodes", C.c_int), ("claim_order", C.c_int), ("ring_entries", C.c_int), ("iow_bvh", C.c_int),

@@ -12,9 +12,9 @@ import rt_amd as R
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared():
+def _declared(headers=("rt_hip.h", "rt_hip_debug.h", "rt_scene.h")):
     names = set()
-    for h in ("rt_hip.h", "rt_scene.h"):
+    for h in headers:
         src = open(os.path.join(ROOT, "include", h)).read()
         src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
         for m in re.finditer(r"^\s*(?:int|void|size_t|rt_dev_scene\s*\*|rt_group\s*\*)\s*\*?\s*(rt_\w+)\s*\(", src, re.M):
@@ -29,6 +29,12 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert declared == set(R.SIGNATURES), declared ^ set(R.SIGNATURES)
+
+
+def test_render_header_declares_no_debug_symbol():
+    """The diagnostics and test hooks live in rt_hip_debug.h; rt_hip.h alone is the render ABI."""
+    assert not [n for n in _declared(("rt_hip.h",)) if n.startswith("rt_debug_")]
+    assert [n for n in _declared(("rt_hip_debug.h",)) if n.startswith("rt_debug_")]
 
 
 def test_abi_version():
