@@ -333,6 +333,50 @@ int rt_render_tiles_async(rt_dev_scene *s, const rt_camera *cam, const rt_params
 int rt_render_image_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p,
                           float *d_rgba, float *d_depth, uint64_t *d_counters, void *stream);
 
+/* ---- ray queries -------------------------------------------------------------------------
+ * Batched closest-hit queries on an INW device scene: what does this ray hit?  (Picking,
+ * visibility and collision probes, debugging a pixel.)  A query's result is what the reference
+ * shader's closest-hit walk leaves behind -- layout 1: 01_BoundingVolumeHierarchy/
+ * computeShaderSrc.glsl:431-473 with IntersectRay :230-269; layout 4: 04_Lights_Camera_And_Action/
+ * computeShaderSrc.glsl:524-563 -- started on an EMPTY 40-float stack with t_limiting = tmax, the
+ * object positions of time ratio `ratio` (0..1, the shader's sample index / samples), and the child
+ * order RT_TRACE_INVERT selects (set: the order the shader takes when dot(u_Camera.Direction,
+ * (1,1,1)) > 0).  The kernel runs the render path's own walk (the scene's options apply: wide
+ * walk, time-bin trees, sphere records, compact nodes, stackless walks, fused cull), so results
+ * are bit-identical whatever the options.
+ *   - A query hits if and only if t_limiting ended below tmax.  Hit: t = the final t_limiting,
+ *     id = the object's index, n = the world-space normal the shader computes (IntersectRay),
+ *     extra = record float 19 (layout 4: the object's refractive index).  Miss: t = tmax exactly
+ *     as passed, id = -1, n = 0, extra = 0.  pad is written as 0.
+ *   - Exact ties in t go to the object the reference's depth-first order reaches first for that
+ *     child order.
+ *   - A push the reference's full stack would drop is dropped here too (the result is then the
+ *     reference's, not the geometric closest hit) and counted in counters[4].
+ *   - tmax <= 0 or NaN: a miss by the shader's own tests (t > 0 && t < t_limiting); no walk runs.
+ *   - A direction with zero or non-finite components gives what the reference walk gives (its
+ *     reciprocals are infinite or NaN; the box tests then follow IEEE min / max).
+ *   - RT_TRACE_ANY (occlusion): id >= 0 exactly when the closest-hit query hits; id is then some
+ *     accepted object and t its t, t_closest <= t < tmax; n = 0 and extra = 0.
+ *   - counters (6 x u64 as rt_stats' first six fields, added to): [0] += n_rays; [1], [2] the node
+ *     visits and primitive tests of the walks that ran (they depend on the options, as in the
+ *     renders); [4] += dropped pushes; [3] and [5] untouched.
+ * Returns RT_E_ARG for a null scene, null rays or hits with n_rays > 0, unknown flag bits,
+ * n_rays > 2^31 or a scene a failed update left broken; RT_E_UNSUPPORTED for an IOW-03 scene;
+ * n_rays == 0 returns RT_OK and launches nothing.  Calls on one scene must not overlap each other
+ * or its renders (they share the scene's work queue). */
+typedef struct rt_ray { float o[3]; float tmax; float d[3]; float ratio; } rt_ray;                /* 32 B */
+typedef struct rt_hit { float t; int32_t id; float n[3]; float extra; uint32_t pad[2]; } rt_hit;  /* 32 B */
+#define RT_TRACE_INVERT 1   /* child order of the shader's walk: its dot(camDir,(1,1,1)) > 0 case */
+#define RT_TRACE_ANY    2   /* occlusion query: may stop at the first accepted hit */
+/* Device pointers (16-byte aligned); never allocates or synchronises (as rt_render_image_async). */
+int rt_trace_rays_async(rt_dev_scene *s, const rt_ray *d_rays, uint32_t n_rays, int flags,
+                        rt_hit *d_hits, uint64_t *d_counters /* 6 x u64, added to; may be NULL */, void *stream);
+/* Blocking: host buffers; builds a device scene for the call (like rt_render_inw) from the
+ * GeometryBuff records and LBVH nodes.  st (may be NULL): the counters and the kernel's device time.
+ * RT_E_ARG also for null geom / nodes, n == 0 or a layout other than 1 and 4. */
+int rt_trace_inw(const float *geom, uint32_t n, int layout, const float *nodes, const rt_ray *rays,
+                 uint32_t n_rays, int flags, rt_hit *hits, int device, rt_stats *st);
+
 /* ---- multi-GPU partition (BASELINE configs[3]) -----------------------------
  * One host thread drives several devices of this process: the frame's tiles are dealt
  * across the devices, each renders its share with rt_render_tiles_async on a stream of its own,

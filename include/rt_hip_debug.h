@@ -121,6 +121,10 @@ int rt_debug_time_bins(const float *nodes, const float *geom, uint32_t n, uint32
                        uint32_t wnodes_cap, uint32_t info[4]);
 int rt_debug_bin_boxes(const float *geom, uint32_t n, uint32_t bins, uint32_t b, float *boxes_out);
 int rt_debug_sphere_records(const float *geom, uint32_t n, int layout, float *out);
+/* The ray-query kernel (rt_trace_rays_async) as the loaded code object has it: info = {VGPRs,
+ * scratch bytes per lane, static LDS bytes per block, resident 256-lane blocks per CU} of the
+ * closest-hit (any = 0) or RT_TRACE_ANY instance, with the fused cull or without.  Needs a device. */
+int rt_debug_trace_kernel(int any, int fused, int info[4]);
 
 #ifdef __cplusplus
 }

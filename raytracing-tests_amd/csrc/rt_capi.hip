@@ -2249,6 +2249,85 @@ int rt_render_image_async(rt_dev_scene *s, const rt_camera *cam, const rt_params
     return launch_scene(s, f, static_cast<hipStream_t>(stream));
 }
 
+// ------------------------------------------------------------------------ ray queries
+int rt_trace_rays_async(rt_dev_scene *s, const rt_ray *d_rays, uint32_t n_rays, int flags, rt_hit *d_hits,
+                        uint64_t *d_counters, void *stream) {
+    static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 32, "rt_ray / rt_hit are 2 float4 each");
+    if (!s || (flags & ~(RT_TRACE_INVERT | RT_TRACE_ANY))) return RT_E_ARG;
+    if (s->kind == 3) return RT_E_UNSUPPORTED;
+    if (s->broken || n_rays > (1u << 31)) return RT_E_ARG;
+    if (n_rays == 0) return RT_OK;
+    if (!d_rays || !d_hits) return RT_E_ARG;
+    rtk::InwScene sc{s->hot.as<float4>(), s->cold.as<float4>(), s->nodes.as<float4>(),
+                     s->lights.as<float>(), s->n, s->n_lights, s->layout, s->sunflower.as<float>(),
+                     s->tex.as<float4>(), s->tex_info.as<int4>(), s->n_tex};
+    set_wide(s, sc);
+    // as in the renders, only layout-1 walks read the sphere records (INW-04's kernels compile them out)
+    if (s->layout == 4) sc.sph = nullptr;
+    // the fused cull under the render path's rule (launch_scene_inw_fold): the scene's culling
+    // boxes within 1000 of the origin; the kernel checks each query's origin
+    sc.fused = (s->opt.inw_fused_cull && sc.wnodes && s->wbound <= 1000.0f) ? 1 : 0;
+    // its own queue counter, past the fold kernels' (two queues 64 B apart and 8 XCD queues from byte 256)
+    unsigned *queue = s->counter.as<unsigned>() + 240;
+    const hipError_t e = rtk::launch_inw_trace(sc, reinterpret_cast<const float4 *>(d_rays), n_rays,
+                                               (flags & RT_TRACE_INVERT) != 0, (flags & RT_TRACE_ANY) != 0,
+                                               reinterpret_cast<float4 *>(d_hits),
+                                               reinterpret_cast<unsigned long long *>(d_counters), queue, s->cus,
+                                               static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) {
+        std::fprintf(stderr, "[rt_hip] launch failed: %s\n", hipGetErrorString(e));
+        return RT_E_HIP;
+    }
+    return RT_OK;
+}
+
+int rt_trace_inw(const float *geom, uint32_t n, int layout, const float *nodes, const rt_ray *rays, uint32_t n_rays,
+                 int flags, rt_hit *hits, int device, rt_stats *st) {
+    if (!geom || !nodes || n == 0 || (layout != 1 && layout != 4)) return RT_E_ARG;
+    if ((flags & ~(RT_TRACE_INVERT | RT_TRACE_ANY)) || n_rays > (1u << 31)) return RT_E_ARG;
+    if (n_rays > 0 && (!rays || !hits)) return RT_E_ARG;
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    std::unique_ptr<rt_dev_scene> s(new (std::nothrow) rt_dev_scene());
+    if (!s) return RT_E_ARG;
+    (void)hipGetDevice(&s->device);
+    try {  // the host builders allocate: no exception crosses the ABI
+        rc = make_inw(s.get(), geom, n, layout, nodes, nullptr, 0, nullptr, 0, 1);
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    if (rc != RT_OK) return rc;
+    if (st) std::memset(st, 0, sizeof(*st));
+    if (n_rays == 0) return RT_OK;
+    DevBuf d_rays, d_hits, d_ctr;
+    const size_t bytes = size_t(n_rays) * sizeof(rt_ray);
+    HIP_OK(d_rays.alloc(bytes));
+    HIP_OK(d_hits.alloc(bytes));
+    HIP_OK(d_ctr.alloc(6 * sizeof(unsigned long long)));
+    HIP_OK(hipMemcpy(d_rays.p, rays, bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(d_ctr.p, 0, 6 * sizeof(unsigned long long)));
+    double ms = 0.0;
+    rc = timed([&] { return rt_trace_rays_async(s.get(), d_rays.as<rt_ray>(), n_rays, flags, d_hits.as<rt_hit>(),
+                                                d_ctr.as<uint64_t>(), nullptr); }, &ms);
+    if (rc != RT_OK) return rc;
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(hits, d_hits.p, bytes, hipMemcpyDeviceToHost));
+    if (st) {
+        unsigned long long c[6];
+        HIP_OK(hipMemcpy(c, d_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
+        st->segments = c[0]; st->node_visits = c[1]; st->prim_tests = c[2];
+        st->shadow_queries = c[3]; st->stack_drops = c[4]; st->nan_drops = c[5];
+        st->ms = ms;
+    }
+    return RT_OK;
+}
+
+int rt_debug_trace_kernel(int any, int fused, int info[4]) {
+    if (!info) return RT_E_ARG;
+    HIP_OK(rtk::inw_trace_kernel_info(any != 0, fused != 0, info));
+    return RT_OK;
+}
+
 // ------------------------------------------------------------------------ rt_scene.h
 int rt_scene_preset(int preset, uint32_t seed, int n_hint, rt_geom_desc *out, int cap, rt_cam_desc *cam,
                     rt_params *params) {

@@ -403,6 +403,14 @@ hipError_t launch_inw_fold(const Frame &f, const InwScene &sc, float4 *ring, uin
                            uint32_t *cost, hipStream_t s);
 // the pixel beams of a pixel-major frame (sc.beam*; exits when the probe picks sample-major)
 hipError_t launch_inw_beam(const Frame &f, const InwScene &sc, const uint32_t *mode, uint32_t force, hipStream_t s);
+// rt_trace.hip: n_rays closest-hit queries (rt_ray / rt_hit as 2 float4 each) on a persistent grid
+// of at most cus * inw_trace_blocks_per_cu blocks; queue: one u32 (zeroed here); counters: 6 x u64
+// added to (slots 0, 1, 2, 4), or null.  sc.fused picks the fused-cull instance.
+hipError_t launch_inw_trace(const InwScene &sc, const float4 *rays, uint32_t n_rays, bool invert, bool any,
+                            float4 *hits, unsigned long long *counters, unsigned *queue, int cus, hipStream_t s);
+int inw_trace_blocks_per_cu(bool any, bool fused);
+// k_inw_trace's {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} (hipFuncGetAttributes)
+hipError_t inw_trace_kernel_info(bool any, bool fused, int info[4]);
 // resident blocks per CU of the render kernel for `kind` (3 = IOW-03 wide, 4 = IOW-03 narrow,
 // 11/14 = INW layout 1/4)
 int resident_blocks_per_cu(int kind);  // 5 = sample-parallel IOW-03, 6/7 = sample-parallel INW 1/4,

@@ -191,6 +191,11 @@ SIGNATURES = {
     "rt_debug_bin_boxes": (C.c_int, [_FP, C.c_uint32, C.c_uint32, C.c_uint32, _FP]),
     "rt_debug_sphere_records": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP]),
     "rt_group_free": (None, [C.c_void_p]),
+    "rt_trace_rays_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "rt_trace_inw": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int,
+                               C.POINTER(RtStats)]),
+    "rt_debug_trace_kernel": (C.c_int, [C.c_int, C.c_int, _IP]),
     "rt_render_multi_async": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
@@ -503,6 +508,32 @@ def render(sc: Scene, params: RtParams | None = None, sphere=None):
                                    C.byref(sc.camera), C.byref(p), fptr(rgba), fptr(depth), C.byref(st))
     check(rc, "render")
     return rgba, depth, st.as_dict()
+
+
+# ----------------------------------------------------------------------- ray queries
+# rt_ray / rt_hit (include/rt_hip.h), 32 bytes each
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("ratio", np.float32)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("id", np.int32), ("n", np.float32, 3), ("extra", np.float32),
+                      ("pad", np.uint32, 2)])
+RT_TRACE_INVERT, RT_TRACE_ANY = 1, 2
+
+
+def trace(sc: Scene, rays: np.ndarray, flags: int = 0, device: int = -1):
+    """rt_trace_inw: blocking closest-hit queries of `rays` (RAY_DTYPE) on a packed INW scene;
+    returns (hits (HIT_DTYPE), stats dict)."""
+    rays = np.ascontiguousarray(rays, RAY_DTYPE)
+    hits = np.zeros(rays.shape, HIT_DTYPE)
+    st = RtStats()
+    check(load().rt_trace_inw(fptr(sc.geom), sc.n, sc.layout, fptr(sc.nodes), rays.ctypes.data, rays.size, int(flags),
+                              hits.ctypes.data, device, C.byref(st)), "rt_trace_inw")
+    return hits, st.as_dict()
+
+
+def trace_kernel_info(any_hit: bool = False, fused: bool = True) -> dict:
+    """rt_debug_trace_kernel: the query kernel's registers, scratch, LDS and resident blocks per CU."""
+    info = (C.c_int * 4)()
+    check(load().rt_debug_trace_kernel(int(any_hit), int(fused), info), "rt_debug_trace_kernel")
+    return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
 
 
 def render_iow01(camera: RtCamera, sphere, params: RtParams):

@@ -1,0 +1,173 @@
+"""Regenerate tests/golden/trace_*.npz: scenes, 2048 ray queries each, and the reference answers
+of tests/trace_ref.c (the CPU oracle's closest-hit walk per query) for both child orders.
+
+Each fixture is self-contained: geom (N, 28), aabbs (N, 6), nodes (2N - 1, 8), layout, rays
+(Q, 8 float32 = rt_ray), hits0 / hits1 (Q, 8 uint32 = rt_hit, invert 0 / 1) and ctr0 / ctr1
+(node visits, primitive tests, dropped pushes of the reference walk).  Run from the repo root
+(needs gcc and the built librt_hip.so for the packers and the host LBVH; no GPU):
+    python tests/golden/make_trace_golden.py
+"""
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "raytracing-tests_amd"), os.path.dirname(HERE)]
+
+import rt_amd as R  # noqa: E402
+import trace_ref as T  # noqa: E402
+
+Q = 2048
+FAR = 32000.0
+
+
+def _pack(objs, stage=R.RT_STAGE_INW01):
+    """objs: (type, position, last_position, rotation_deg, scale) -> geom, aabbs, nodes."""
+    arr = (R.RtGeomDesc * len(objs))()
+    for d, (ty, pos, last, rot, scale) in zip(arr, objs):
+        d.type = ty
+        for k in range(3):
+            d.position[k], d.last_position[k] = float(pos[k]), float(last[k])
+            d.rotation_deg[k], d.scale[k] = float(rot[k]), float(scale[k])
+            d.color[k] = 0.5
+        d.refractivity, d.reflectivity, d.refractive_index = 0.3, 0.3, 1.5
+    out = R.pack(arr, len(objs), stage)
+    return out["geom"], out["aabbs"], out["nodes"]
+
+
+def _spheres(rng, n, half=(20.0, 3.0, 20.0), r=(0.3, 1.2), move=0.4):
+    objs = []
+    for _ in range(n):
+        p = rng.uniform(-1, 1, 3) * half
+        s = rng.uniform(*r)
+        objs.append((R.RT_INW_ELLIPSOID, p, p - rng.uniform(-move, move, 3), (0, 0, 0), (s, s, s)))
+    return objs
+
+
+def scene_spheres1500(shift=False):
+    objs = _spheres(np.random.default_rng(11), 1500)
+    if shift:  # the same objects one frame later: every position (and last position) moved
+        rng = np.random.default_rng(12)
+        objs = [(ty, p + dp, l + dp, rot, s) for (ty, p, l, rot, s) in objs for dp in [rng.uniform(-1.0, 1.0, 3)]]
+    return _pack(objs), 1
+
+
+def scene_mixed700():
+    rng = np.random.default_rng(21)
+    objs = []
+    for i in range(700):
+        p = rng.uniform(-1, 1, 3) * (12.0, 3.0, 12.0)
+        last = p - rng.uniform(-0.4, 0.4, 3) if i % 3 == 0 else p
+        objs.append((R.RT_INW_ELLIPSOID if i % 2 == 0 else R.RT_INW_CUBOID, p, last, rng.uniform(-90, 90, 3),
+                     rng.uniform(0.3, 2.0, 3)))
+    return _pack(objs), 1
+
+
+def scene_small(n, seed):
+    return _pack(_spheres(np.random.default_rng(seed), n, half=(2.0, 1.0, 2.0), r=(0.5, 1.2), move=0.2)), 1
+
+
+def scene_dups300():
+    objs = _spheres(np.random.default_rng(41), 150, half=(8.0, 2.0, 8.0), r=(0.4, 1.2), move=0.0)
+    return _pack(objs + objs), 1  # object i and i + 150 coincide: every hit ties in t
+
+
+def scene_pile120():
+    rng = np.random.default_rng(51)
+    z = np.zeros(3)
+    objs = [(R.RT_INW_ELLIPSOID, z, z, z, (0.2 + 0.05 * i,) * 3) for i in range(80)]
+    objs += _spheres(rng, 40, half=(6.0, 2.0, 6.0), r=(0.3, 0.8), move=0.0)
+    return _pack(objs), 1
+
+
+def scene_refset4():
+    sc = R.make_scene(R.PRESET_INW04_REFSET, spp=1)
+    return (sc.geom, sc.aabbs, sc.nodes), 4
+
+
+SCENES = {
+    "spheres1500": lambda: scene_spheres1500(),
+    "spheres1500_b": lambda: scene_spheres1500(shift=True),
+    "mixed700": scene_mixed700,
+    "one": lambda: scene_small(1, 31),
+    "three": lambda: scene_small(3, 33),
+    "dups300": scene_dups300,
+    "pile120": scene_pile120,
+    "refset4": scene_refset4,
+}
+SEEDS = {name: 100 + i for i, name in enumerate(SCENES)}
+
+
+def _unit(v):
+    return v / np.linalg.norm(v)
+
+
+def make_rays(geom, aabbs, seed, n=Q):
+    """Eight kinds in turn, time ratios k / 16."""
+    rng = np.random.default_rng(seed)
+    lo, hi = aabbs[:, :3].min(0).astype(np.float64), aabbs[:, 3:].max(0).astype(np.float64)
+    mid, ext = (lo + hi) / 2, np.maximum((hi - lo) / 2, 1.0)
+    rays = np.zeros(n, T.RAY_DTYPE)
+    for q in range(n):
+        kind, ratio = q % 8, ((q // 8) % 17) / 16.0
+        g = int(rng.integers(len(geom)))
+        f = geom[g].astype(np.float64)
+        centre = f[0:3] - f[15:18] * (1.0 - ratio)  # the object's position at this time ratio
+        scale = f[12:15]
+        tmax = FAR
+        o = mid + ext * 1.5 * _unit(rng.normal(size=3))  # on a shell around the scene
+        if kind == 0:    # anywhere, any direction
+            o = mid + ext * rng.uniform(-1.3, 1.3, 3)
+            d = _unit(rng.normal(size=3))
+        elif kind == 1:  # starts inside an object
+            o = centre + 0.2 * scale * rng.uniform(-1, 1, 3)
+            d = _unit(rng.normal(size=3))
+        elif kind in (2, 3):  # aimed near an object, kind 3 with a limit around the target's distance
+            target = centre + 1.2 * scale * rng.uniform(-1, 1, 3)
+            d = _unit(target - o)
+            if kind == 3:
+                tmax = rng.uniform(0.2, 1.1) * np.linalg.norm(target - o)
+        elif kind == 4:  # along an axis through an object: two zero direction components
+            k, sgn = int(rng.integers(3)), float(rng.choice((-1.0, 1.0)))
+            o = centre + 0.3 * scale * rng.uniform(-1, 1, 3)
+            o[k] -= sgn * (ext[k] * 2.5 + 1.0)
+            d = np.zeros(3)
+            d[k] = sgn
+        elif kind == 5:  # not normalised
+            d = _unit(centre + 0.3 * scale * rng.uniform(-1, 1, 3) - o) * 10.0 ** rng.uniform(-2.0, np.log10(50.0))
+        else:            # plainly aimed
+            d = _unit(centre + 0.3 * scale * rng.uniform(-1, 1, 3) - o)
+        rays[q]["o"], rays[q]["d"] = o.astype(np.float32), d.astype(np.float32)
+        rays[q]["tmax"], rays[q]["ratio"] = np.float32(tmax), np.float32(ratio)
+    return rays
+
+
+def main():
+    only = set(sys.argv[1:])
+    with tempfile.TemporaryDirectory() as tmp:
+        lib = T.build(tmp)
+        for name in T.SCENES:
+            if only and name not in only:
+                continue
+            (geom, aabbs, nodes), layout = SCENES[name]()
+            rays = make_rays(geom, aabbs, SEEDS[name])
+            out = {"geom": geom, "aabbs": aabbs, "nodes": nodes, "layout": np.int32(layout),
+                   "rays": rays.view(np.float32).reshape(-1, 8)}
+            for inv in (0, 1):
+                hits, ctr = T.run(lib, geom, nodes, layout, rays, inv)
+                out[f"hits{inv}"] = hits.view(np.uint32).reshape(-1, 8)
+                out[f"ctr{inv}"] = ctr
+            path = os.path.join(HERE, f"trace_{name}.npz")
+            np.savez_compressed(path, **out)
+            h0, h1 = out["hits0"].view(T.HIT_DTYPE).reshape(-1), out["hits1"].view(T.HIT_DTYPE).reshape(-1)
+            print(name, "n", len(geom), "hit fraction", round(float((h0["id"] >= 0).mean()), 3),
+                  "id differs", int((h0["id"] != h1["id"]).sum()),
+                  "t differs", int((h0["t"].view(np.uint32) != h1["t"].view(np.uint32)).sum()),
+                  "drops", int(out["ctr0"][2]), int(out["ctr1"][2]), "bytes", os.path.getsize(path))
+
+
+if __name__ == "__main__":
+    main()
