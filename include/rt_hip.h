@@ -361,7 +361,8 @@ int rt_render_image_async(rt_dev_scene *s, const rt_camera *cam, const rt_params
  *     visits and primitive tests of the walks that ran (they depend on the options, as in the
  *     renders); [4] += dropped pushes; [3] and [5] untouched.
  * Returns RT_E_ARG for a null scene, null rays or hits with n_rays > 0, unknown flag bits,
- * n_rays > 2^31 or a scene a failed update left broken; RT_E_UNSUPPORTED for an IOW-03 scene;
+ * n_rays > 2^31 or a scene a failed update left broken; RT_E_UNSUPPORTED for an IOW-03 scene (those
+ * have rt_trace_iow_rays_async, below);
  * n_rays == 0 returns RT_OK and launches nothing.  Calls on one scene must not overlap each other
  * or its renders (they share the scene's work queue). */
 typedef struct rt_ray { float o[3]; float tmax; float d[3]; float ratio; } rt_ray;                /* 32 B */
@@ -376,6 +377,42 @@ int rt_trace_rays_async(rt_dev_scene *s, const rt_ray *d_rays, uint32_t n_rays, 
  * RT_E_ARG also for null geom / nodes, n == 0 or a layout other than 1 and 4. */
 int rt_trace_inw(const float *geom, uint32_t n, int layout, const float *nodes, const rt_ray *rays,
                  uint32_t n_rays, int flags, rt_hit *hits, int device, rt_stats *st);
+
+/* ---- ray queries, IOW-03 ------------------------------------------------------------------
+ * The same question on an IOW-03 device scene.  rt_ray and rt_hit are reused.  A query's result is
+ * what the reference shader's LaunchRay (03_Shadows_and_Materials/computeShaderSrc.glsl:196-256)
+ * computes for (o, d, max_t = tmax); rt_ray.ratio is ignored, any bit pattern may be in it.  The
+ * kernel runs the render path's own search (the scene's options apply: iow_linear, iow_lds_bvh,
+ * iow_leaf_batch), so results are bit-identical whatever the options.
+ *   - A query hits if and only if min_t ended below tmax.  Hit: t = the final min_t, id = the
+ *     object's index, n = RayReturnData.normal (world space, normalised), extra = record float 20
+ *     (the object's refractive index, material.z).  Miss: t = tmax exactly as passed, id = -1,
+ *     n = 0, extra = 0.  pad is written as 0.
+ *   - What t measures: t is the shader's own min_t, a distance along normalize(M * d) in the hit
+ *     object's frame, NOT the parameter of d.  The hit point is o + d * t, as the shader forms it.
+ *     t equals the usual ray parameter only for unit d and an orthonormal M.
+ *   - Exact ties in t go to the lowest object index (the reference's strict min_t > t).
+ *   - tmax <= 0 or NaN: a miss by the shader's own test (min_t > t && t > 0); no walk runs.
+ *   - A zero or NaN direction is a miss: every object's t is -1.
+ *   - Directions with |d|^2 outside (0.998, 1.002) are answered by the reference's linear loop, as
+ *     in the renders: exact, but n object tests per query.  Normalise directions to get the BVH.
+ *   - RT_TRACE_ANY: as above (id >= 0 exactly when the closest-hit query hits, t_closest <= t <
+ *     tmax, n = 0, extra = 0).  RT_TRACE_INVERT has no meaning here: any bit other than
+ *     RT_TRACE_ANY is an error.
+ *   - counters: [0] += n_rays; [1], [2] the node visits and object tests of the searches that ran
+ *     (they depend on the options); [3], [4], [5] untouched.
+ * Returns RT_E_ARG for a null scene, null rays or hits with n_rays > 0, a flag bit other than
+ * RT_TRACE_ANY or n_rays > 2^31; RT_E_UNSUPPORTED for an INW scene; n_rays == 0 returns RT_OK and
+ * launches nothing.  Every argument error comes back before a device is touched.  Calls on one
+ * scene must not overlap each other or its renders (they share the scene's work queue). */
+/* Device pointers (16-byte aligned); never allocates or synchronises. */
+int rt_trace_iow_rays_async(rt_dev_scene *s, const rt_ray *d_rays, uint32_t n_rays, int flags,
+                            rt_hit *d_hits, uint64_t *d_counters /* 6 x u64, added to; may be NULL */, void *stream);
+/* Blocking: host buffers; builds a device scene for the call, like rt_render_iow03, from the
+ * ObjectTypes and N*24 record buffers.  st (may be NULL): the counters and the kernel's device time.
+ * RT_E_ARG also for null types / records or n == 0. */
+int rt_trace_iow03(const float *types, const float *records /* N*24 */, uint32_t n, const rt_ray *rays,
+                   uint32_t n_rays, int flags, rt_hit *hits, int device, rt_stats *st);
 
 /* ---- multi-GPU partition (BASELINE configs[3]) -----------------------------
  * One host thread drives several devices of this process: the frame's tiles are dealt

@@ -125,6 +125,9 @@ int rt_debug_sphere_records(const float *geom, uint32_t n, int layout, float *ou
  * scratch bytes per lane, static LDS bytes per block, resident 256-lane blocks per CU} of the
  * closest-hit (any = 0) or RT_TRACE_ANY instance, with the fused cull or without.  Needs a device. */
 int rt_debug_trace_kernel(int any, int fused, int info[4]);
+/* The same for the IOW-03 ray-query kernel (rt_trace_iow_rays_async): lds = 1 the instance with
+ * the BVH staged in LDS, 0 the one that reads nodes from global memory (also the linear loop's). */
+int rt_debug_trace_iow_kernel(int any, int lds, int info[4]);
 
 #ifdef __cplusplus
 }

@@ -2328,6 +2328,78 @@ int rt_debug_trace_kernel(int any, int fused, int info[4]) {
     return RT_OK;
 }
 
+int rt_trace_iow_rays_async(rt_dev_scene *s, const rt_ray *d_rays, uint32_t n_rays, int flags, rt_hit *d_hits,
+                            uint64_t *d_counters, void *stream) {
+    if (!s || (flags & ~RT_TRACE_ANY)) return RT_E_ARG;
+    if (s->kind != 3) return RT_E_UNSUPPORTED;
+    if (n_rays > (1u << 31)) return RT_E_ARG;
+    if (n_rays == 0) return RT_OK;
+    if (!d_rays || !d_hits) return RT_E_ARG;
+    // as launch_scene builds it; the sample tables stay unread
+    const rtk::IowScene sc{s->hot.as<float>(), s->cold.as<float>(), s->n, s->nodes.as<float4>(),
+                           s->sunflower.as<float>(), s->fib.as<float>(), s->ring.as<int>(), s->root_link,
+                           s->obox.as<float4>(), s->n_wide, s->opt.iow_lds_bvh};
+    // the ray queries' own queue counter (rt_trace_rays_async: past the fold kernels')
+    unsigned *queue = s->counter.as<unsigned>() + 240;
+    const hipError_t e = rtk::launch_iow_trace(sc, s->opt.iow_leaf_batch, reinterpret_cast<const float4 *>(d_rays),
+                                               n_rays, (flags & RT_TRACE_ANY) != 0,
+                                               reinterpret_cast<float4 *>(d_hits),
+                                               reinterpret_cast<unsigned long long *>(d_counters), queue, s->cus,
+                                               static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) {
+        std::fprintf(stderr, "[rt_hip] launch failed: %s\n", hipGetErrorString(e));
+        return RT_E_HIP;
+    }
+    return RT_OK;
+}
+
+int rt_trace_iow03(const float *types, const float *records, uint32_t n, const rt_ray *rays, uint32_t n_rays,
+                   int flags, rt_hit *hits, int device, rt_stats *st) {
+    if (!types || !records || n == 0) return RT_E_ARG;
+    if ((flags & ~RT_TRACE_ANY) || n_rays > (1u << 31)) return RT_E_ARG;
+    if (n_rays > 0 && (!rays || !hits)) return RT_E_ARG;
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    std::unique_ptr<rt_dev_scene> s(new (std::nothrow) rt_dev_scene());
+    if (!s) return RT_E_ARG;
+    (void)hipGetDevice(&s->device);
+    try {  // the host builder allocates: no exception crosses the ABI
+        rc = make_iow03(s.get(), types, records, n, 1);  // spp = 1: the sample tables are unused
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    if (rc != RT_OK) return rc;
+    if (st) std::memset(st, 0, sizeof(*st));
+    if (n_rays == 0) return RT_OK;
+    DevBuf d_rays, d_hits, d_ctr;
+    const size_t bytes = size_t(n_rays) * sizeof(rt_ray);
+    HIP_OK(d_rays.alloc(bytes));
+    HIP_OK(d_hits.alloc(bytes));
+    HIP_OK(d_ctr.alloc(6 * sizeof(unsigned long long)));
+    HIP_OK(hipMemcpy(d_rays.p, rays, bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(d_ctr.p, 0, 6 * sizeof(unsigned long long)));
+    double ms = 0.0;
+    rc = timed([&] { return rt_trace_iow_rays_async(s.get(), d_rays.as<rt_ray>(), n_rays, flags, d_hits.as<rt_hit>(),
+                                                    d_ctr.as<uint64_t>(), nullptr); }, &ms);
+    if (rc != RT_OK) return rc;
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(hits, d_hits.p, bytes, hipMemcpyDeviceToHost));
+    if (st) {
+        unsigned long long c[6];
+        HIP_OK(hipMemcpy(c, d_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
+        st->segments = c[0]; st->node_visits = c[1]; st->prim_tests = c[2];
+        st->shadow_queries = c[3]; st->stack_drops = c[4]; st->nan_drops = c[5];
+        st->ms = ms;
+    }
+    return RT_OK;
+}
+
+int rt_debug_trace_iow_kernel(int any, int lds, int info[4]) {
+    if (!info) return RT_E_ARG;
+    HIP_OK(rtk::iow_trace_kernel_info(any != 0, lds != 0, info));
+    return RT_OK;
+}
+
 // ------------------------------------------------------------------------ rt_scene.h
 int rt_scene_preset(int preset, uint32_t seed, int n_hint, rt_geom_desc *out, int cap, rt_cam_desc *cam,
                     rt_params *params) {

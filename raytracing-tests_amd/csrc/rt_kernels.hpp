@@ -411,6 +411,14 @@ hipError_t launch_inw_trace(const InwScene &sc, const float4 *rays, uint32_t n_r
 int inw_trace_blocks_per_cu(bool any, bool fused);
 // k_inw_trace's {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} (hipFuncGetAttributes)
 hipError_t inw_trace_kernel_info(bool any, bool fused, int info[4]);
+// rt_trace_iow.hip: n_rays closest-hit queries on an IOW-03 scene, same persistent grid and buffers
+// (counters: slots 0, 1, 2).  iow_lds(sc) picks the LDS-staged instance; sc.nodes == null runs the
+// linear loop; leaf_batch = rt_options.iow_leaf_batch.
+hipError_t launch_iow_trace(const IowScene &sc, int leaf_batch, const float4 *rays, uint32_t n_rays, bool any,
+                            float4 *hits, unsigned long long *counters, unsigned *queue, int cus, hipStream_t s);
+int iow_trace_blocks_per_cu(bool any, bool ln);
+// k_iow_trace's {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} (hipFuncGetAttributes)
+hipError_t iow_trace_kernel_info(bool any, bool ln, int info[4]);
 // resident blocks per CU of the render kernel for `kind` (3 = IOW-03 wide, 4 = IOW-03 narrow,
 // 11/14 = INW layout 1/4)
 int resident_blocks_per_cu(int kind);  // 5 = sample-parallel IOW-03, 6/7 = sample-parallel INW 1/4,

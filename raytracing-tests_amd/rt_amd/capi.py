@@ -196,6 +196,11 @@ SIGNATURES = {
     "rt_trace_inw": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int,
                                C.POINTER(RtStats)]),
     "rt_debug_trace_kernel": (C.c_int, [C.c_int, C.c_int, _IP]),
+    "rt_trace_iow_rays_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "rt_trace_iow03": (C.c_int, [_FP, _FP, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int,
+                                 C.POINTER(RtStats)]),
+    "rt_debug_trace_iow_kernel": (C.c_int, [C.c_int, C.c_int, _IP]),
     "rt_render_multi_async": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
@@ -533,6 +538,24 @@ def trace_kernel_info(any_hit: bool = False, fused: bool = True) -> dict:
     """rt_debug_trace_kernel: the query kernel's registers, scratch, LDS and resident blocks per CU."""
     info = (C.c_int * 4)()
     check(load().rt_debug_trace_kernel(int(any_hit), int(fused), info), "rt_debug_trace_kernel")
+    return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
+
+
+def trace_iow(sc: Scene, rays: np.ndarray, flags: int = 0, device: int = -1):
+    """rt_trace_iow03: blocking closest-hit queries of `rays` (RAY_DTYPE) on a packed IOW-03 scene;
+    returns (hits (HIT_DTYPE), stats dict)."""
+    rays = np.ascontiguousarray(rays, RAY_DTYPE)
+    hits = np.zeros(rays.shape, HIT_DTYPE)
+    st = RtStats()
+    check(load().rt_trace_iow03(fptr(sc.types), fptr(sc.records), sc.n, rays.ctypes.data, rays.size, int(flags),
+                                hits.ctypes.data, device, C.byref(st)), "rt_trace_iow03")
+    return hits, st.as_dict()
+
+
+def trace_iow_kernel_info(any_hit: bool = False, lds: bool = True) -> dict:
+    """rt_debug_trace_iow_kernel: the IOW-03 query kernel's registers, scratch, LDS and resident blocks per CU."""
+    info = (C.c_int * 4)()
+    check(load().rt_debug_trace_iow_kernel(int(any_hit), int(lds), info), "rt_debug_trace_iow_kernel")
     return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
 
 
