@@ -520,29 +520,9 @@ __device__ __forceinline__ float4 sload4(const float4 *p, int i) {
 // inside its own box, and then skipping it changes nothing; but where an object's face coincides
 // with its box face, rounding can put t an ulp below te.  Any accepted candidate with t < te
 // therefore hands the ray to the reference walk (ok = false).
-// Walk parking (RT_INW_PARK experiment, DESIGN.md §5 "Walk parking"): a wave's walk loop runs
-// as long as its slowest lane; with PK, once at most kParkLanes lanes still walk (after at least
-// kParkMinTrips trips) the wave tests the pending leaves, saves those lanes' walk state to their
-// slot (2 float4: cur, sp, best object, its rank; best t, culling limit) and leaves the loop, so
-// the other lanes shade and start their next segments; the parked lanes resume their walk in the
-// next iteration of the fold kernel, next to the new walks.  The segment's ray stays in the
-// shared stack (the walk's stack starts 8 floats above it).  The walk's result does not depend on
-// when its node steps run, so the image and the counters are unchanged.
-#ifndef RT_INW_PARK_LANES
-#define RT_INW_PARK_LANES 8
-#endif
-#ifndef RT_INW_PARK_MIN
-#define RT_INW_PARK_MIN 4
-#endif
-constexpr int kParkLanes = RT_INW_PARK_LANES, kParkMinTrips = RT_INW_PARK_MIN;
 // Postponed leaves are tested once every walking lane holds one; a smaller batch (once this many
 // lanes hold one) was an experiment, and 65 = more than a wave = off
 constexpr int kInwLeafBatch = 65;
-struct WalkPark {
-    float4 *slot;   // this lane's 2 float4
-    bool resume;    // the walk was parked in an earlier iteration: restore it
-    bool parked;    // out: parked again
-};
 // QN: the quantised nodes (S.qnodes, cull4q; requires FU), LN then meaning the staged ones in g_inw_qlds.
 // The hit object's normal and extra data (01_BVH...glsl:FillHitData's inputs) at t = bt.  SP with
 // sphere records: from their third float4 (RN(1/RN(s*s)) per axis, extra) -- R = I, so the
@@ -585,11 +565,15 @@ __device__ __forceinline__ void inw_hit_normal(const InwScene &S, int bg, f3 o, 
 }
 
 // SP: the sphere-record object test is compiled in (INW-01 kernels; INW-04's keep their registers)
-template <bool WANT_NORMAL, bool LN = false, bool FU = false, bool PK = false, bool QN = false, class KS = FStack,
-          bool SP = true>
+// The trip (one iteration of the loop below) has one divergent region, the node step; the rest of
+// a lane's state machine is selects on integers, so the compiler keeps no loop-carried lane mask
+// to re-merge after every region (DESIGN.md §5.2 "The walk trip").  A lane's state is `cur`: a
+// node (> 0), a leaf (<= 0: object -cur) or kWalkDone (it walks no more: its stack ran empty or
+// overflowed, or the walk's conditions never held for it).
+constexpr int kWalkDone = (-2147483647 - 1);
+template <bool WANT_NORMAL, bool LN = false, bool FU = false, bool QN = false, class KS = FStack, bool SP = true>
 __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float ratio, bool invert, float &tlim,
-                                   f3 &normal, float &extra, float init_geom, Ctr &c, bool &ok,
-                                   WalkPark *wp = nullptr) {
+                                   f3 &normal, float &extra, float init_geom, Ctr &c, bool &ok) {
     static_assert(!QN || FU, "quantised nodes are culled with the fused planes");
     const f3 id = f3{rcp(d.x), rcp(d.y), rcp(d.z)};  // the reference's reciprocals (test_aabb)
     ok = S.wnodes != nullptr && K.size + S.dfs_high <= (uint32_t)kFStack && __builtin_isfinite(id.x) &&
@@ -608,9 +592,9 @@ __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float r
     // float with |o| ~ 10^3 overflows it, and every fma would be -inf or NaN (every child culled);
     // such a ray takes the reference walk
     if (FU) ok = ok && __builtin_isfinite(noid.x) && __builtin_isfinite(noid.y) && __builtin_isfinite(noid.z);
-    // 3 spare slots for branch-free pushes; PK: the segment's ray (8 floats) stays below the walk
+    // 3 spare slots for branch-free pushes
     int cap;
-    float *const wsb = K.walk_stack(PK ? 8u : 0u, 3, cap);  // entry p at wsb[p * kBlock]
+    float *const wsb = K.walk_stack(0u, 3, cap);  // entry p at wsb[p * kBlock]
     const uint32_t ox = d.x < 0.0f ? 3u : 0u, oy = d.y < 0.0f ? 4u : 1u, oz = d.z < 0.0f ? 5u : 2u;
     const WnodeBuf wrs = wnode_buf(S, ox * 16u, oy * 16u, oz * 16u);
     int sp = 0, pend = -1, cur = S.wroot;
@@ -618,20 +602,11 @@ __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float r
         const int b = min((int)(ratio * (float)S.wbins), (int)S.wbins - 1);
         cur = 1 + (int)S.wbin_base + b * (int)S.wbin_stride;
     }
-    bool walking = ok, ovf = false;
+    cur = ok ? cur : kWalkDone;
     float lim = bt * 1.0001f + 1e-3f;
     // the leaf-entry guard: the best hit's leaf-box entry, and the smallest t of the
     // other hits; the reference's walk accepts the best hit for certain when t2 > bte
     float bte = 0.0f, t2 = tlim0;
-    if constexpr (PK) {
-        if (wp->resume) {  // a parked walk: its state from the slot (ok held when it parked)
-            const float4 a = wp->slot[0], b = wp->slot[1];
-            cur = __float_as_int(a.x); sp = __float_as_int(a.y); bg = __float_as_int(a.z); br = __float_as_uint(a.w);
-            bt = b.x; lim = b.y; bte = b.z; t2 = b.w;
-        }
-        wp->parked = false;
-    }
-    int trips = 0;
     auto leaf = [&](int g) {
         c.prims++;
         const float4 n0 = S.leafbox[2 * g], n1 = S.leafbox[2 * g + 1];
@@ -672,85 +647,77 @@ __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float r
         }
     };
     for (;;) {
-        OCC_TALLY(c, kOccWalk, walking);
-        OCC_TALLY(c, kOccNode, walking && cur > 0);
+        OCC_TALLY(c, kOccWalk, cur != kWalkDone);
+        OCC_TALLY(c, kOccNode, cur > 0);
 #ifdef RT_DIAG_OCC
         {  // how often a node step's lanes share one node (a wave-uniform node load would serve them)
-            const unsigned long long m = __ballot(walking && cur > 0);
+            const unsigned long long m = __ballot(cur > 0);
             if (m) {
                 const int c0 = __builtin_amdgcn_readlane(cur, (int)__builtin_ctzll(m));
-                const bool on = walking && cur == c0;
+                const bool on = cur == c0;
                 OCC_TALLY(c, kOccSame, on);
-                if (__ballot(walking && cur > 0 && cur != c0) == 0ull) OCC_TALLY(c, kOccUni, on);
+                if (__ballot(cur > 0 && cur != c0) == 0ull) OCC_TALLY(c, kOccUni, on);
             }
         }
 #endif
-        if (walking) {
-            bool pop;
-            if (cur > 0) {
-                float4 lk;
-                float t0, t1, t2, t3;
-                if constexpr (QN) {
-                    float4 qa, qb, qc;
-                    inw_qnode<LN>(S, cur, qa, qb, qc, lk);
-                    cull4q(qa, qb, qc, ox != 0u, oy != 1u, oz != 2u, fid, noid, lim, t0, t1, t2, t3);
-                } else {
-                    float4 nx, ny, nz, fx, fy, fz;
-                    inw_wnode_nf_buf<LN>(S, wrs, cur, ox * 16u, oy * 16u, oz * 16u, nx, ny, nz, fx, fy, fz, lk);
-                    cull4nf<FU>(nx, ny, nz, fx, fy, fz, o, fid, noid, lim, t0, t1, t2, t3);
-                }
-                c.nodes += 4;
-                int k0 = __float_as_int(lk.x), k1 = __float_as_int(lk.y), k2 = __float_as_int(lk.z),
-                    k3 = __float_as_int(lk.w);
-                cswap(t0, k0, t1, k1); cswap(t2, k2, t3, k3);
-                cswap(t0, k0, t2, k2); cswap(t1, k1, t3, k3);
-                cswap(t1, k1, t2, k2);
-                int p = sp;  // branch-free pushes, farthest first (a miss is overwritten before a pop)
-                wsb[p * kBlock] = __int_as_float(k3); p += t3 != kMiss;
-                wsb[p * kBlock] = __int_as_float(k2); p += t2 != kMiss;
-                wsb[p * kBlock] = __int_as_float(k1); p += t1 != kMiss;
-                if (p > cap) { ovf = true; p = cap; }
-                sp = p;
-                cur = k0;
-                pop = t0 == kMiss;
+        // the node step: what it leaves for a lane not on a node is "stay": the same cur and sp,
+        // a nearest child that is no miss
+        int nxt = cur, p = sp;
+        float tn = 0.0f;
+        if (cur > 0) {
+            float4 lk;
+            float c0, c1, c2, c3;
+            if constexpr (QN) {
+                float4 qa, qb, qc;
+                inw_qnode<LN>(S, cur, qa, qb, qc, lk);
+                cull4q(qa, qb, qc, ox != 0u, oy != 1u, oz != 2u, fid, noid, lim, c0, c1, c2, c3);
             } else {
-                pop = pend < 0;  // a leaf waits while the lane still holds one
-                if (pop) pend = -cur;
+                float4 nx, ny, nz, fx, fy, fz;
+                inw_wnode_nf_buf<LN>(S, wrs, cur, ox * 16u, oy * 16u, oz * 16u, nx, ny, nz, fx, fy, fz, lk);
+                cull4nf<FU>(nx, ny, nz, fx, fy, fz, o, fid, noid, lim, c0, c1, c2, c3);
             }
-            if (pop) {
-                if (sp == 0) walking = false;
-                else cur = __float_as_int(wsb[(--sp) * kBlock]);
-            }
-            if (ovf) walking = false;
+            c.nodes += 4;
+            int k0 = __float_as_int(lk.x), k1 = __float_as_int(lk.y), k2 = __float_as_int(lk.z),
+                k3 = __float_as_int(lk.w);
+            cswap(c0, k0, c1, k1); cswap(c2, k2, c3, k3);
+            cswap(c0, k0, c2, k2); cswap(c1, k1, c3, k3);
+            cswap(c1, k1, c2, k2);
+            // branch-free pushes, farthest first (a miss is overwritten before a pop)
+            wsb[p * kBlock] = __int_as_float(k3); p += c3 != kMiss;
+            wsb[p * kBlock] = __int_as_float(k2); p += c2 != kMiss;
+            wsb[p * kBlock] = __int_as_float(k1); p += c1 != kMiss;
+            nxt = k0;
+            tn = c0;
         }
+        // (a lane not on a node keeps p = sp, which is <= cap or -1.  This needs cap >= 0, that is
+        // K.size <= kFStack - 3 at entry: the render kernels walk after pop_ray, size <= 32, the
+        // query kernel at size 0, and GStack's cap is a constant.  With cap < 0 an idle lane would
+        // count as overflowed and go to the reference walk: the same result, for more work)
+        const bool over = p > cap;
+        // a leaf is taken (and the lane pops) unless the lane still holds one: then it waits on it
+        const bool take = cur <= 0 && cur != kWalkDone && pend < 0;
+        pend = take ? -cur : pend;
+        const bool pop = take || tn == kMiss;
+        // every lane reads the entry under its top (its own column: q <= cap + 2, the spare slots;
+        // at p <= 0 a value nobody uses)
+        const int q = max(p - 1, 0);
+        const int top = __float_as_int(wsb[q * kBlock]);
+        cur = pop ? (p > 0 ? top : kWalkDone) : nxt;
+        sp = pop ? q : p;
+        // a push past cap ends the lane's walk; sp = -1 carries the overflow to the end
+        cur = over ? kWalkDone : cur;
+        sp = over ? -1 : sp;
         // postponed leaves are tested once every walking lane holds one (or kInwLeafBatch lanes)
-        if (__all(!walking || pend >= 0) ||
+        if (__all(cur == kWalkDone || pend >= 0) ||
             (kInwLeafBatch < 65 && __popcll(__ballot(pend >= 0)) >= (unsigned)kInwLeafBatch)) {
             OCC_TALLY(c, kOccLeaf, pend >= 0);
             if (pend >= 0) { leaf(pend); pend = -1; }
-            if (__all(!walking)) break;
-        }
-        if constexpr (PK) {
-            if (++trips >= kParkMinTrips && __popcll(__ballot(walking)) <= kParkLanes) {
-                if (__any(pend >= 0)) {  // every pending leaf is tested before the lanes part
-                    OCC_TALLY(c, kOccLeaf, pend >= 0);
-                    if (pend >= 0) { leaf(pend); pend = -1; }
-                }
-                if (ovf) walking = false;
-                if (walking) {
-                    wp->slot[0] = make_float4(__int_as_float(cur), __int_as_float(sp), __int_as_float(bg), __uint_as_float(br));
-                    wp->slot[1] = make_float4(bt, lim, bte, t2);
-                    wp->parked = true;
-                }
-                break;
-            }
+            if (__all(cur == kWalkDone)) break;
         }
     }
-    if (PK && wp->parked) return init_geom;
     // the best hit passes the reference's leaf-box test for certain unless another hit's t could
     // have lowered its running limit to the box entry first (rare: a face on its box, C5)
-    if (bg >= 0 && !(t2 > bte)) ovf = true;
-    if (ovf) ok = false;
+    if (sp < 0 || (bg >= 0 && !(t2 > bte))) ok = false;
     if (!ok) return init_geom;
     if (bg < 0) return init_geom;
     tlim = bt;
@@ -1152,15 +1119,12 @@ __device__ float inw_surrounding_ri_sl(const InwScene &S, f3 hp, float ratio, Ct
 // EO: the reference walks' box test with the shader's early outs (INW-01) or all axes (INW-04)
 // QN: the wide walk reads the quantised nodes (LN: the staged ones); the LBVH walks then read no
 // staged node (their LDS is not filled in the GQ instance)
-template <bool WANT_NORMAL, bool LN = false, bool FU = false, bool PK = false, bool EO = true, bool QN = false,
-          class KS = FStack>
+template <bool WANT_NORMAL, bool LN = false, bool FU = false, bool EO = true, bool QN = false, class KS = FStack>
 __device__ __forceinline__ float inw_closest(const InwScene &S, KS &K, f3 o, f3 d, float ratio, bool invert,
-                                             float &tlim, f3 &normal, float &extra, float init_geom, Ctr &c,
-                                             WalkPark *wp = nullptr) {
+                                             float &tlim, f3 &normal, float &extra, float init_geom, Ctr &c) {
     bool ok = false;
-    const float g = inw_traverse_wide<WANT_NORMAL, LN, FU, PK, QN, KS, EO>(S, K, o, d, ratio, invert, tlim, normal, extra,
-                                                                   init_geom, c, ok, wp);
-    if (PK && wp->parked) return g;
+    const float g = inw_traverse_wide<WANT_NORMAL, LN, FU, QN, KS, EO>(S, K, o, d, ratio, invert, tlim, normal, extra,
+                                                                       init_geom, c, ok);
     OCC_TALLY(c, kOccRef, !ok);
     if (ok) return g;
     c.refw++;

@@ -1410,13 +1410,10 @@ __device__ f3 inw_tex_color(const InwScene &S, uint32_t k, f3 lp) {
 // One iteration of out_Pixel's ray loop (01_BVH...glsl:414-597 / 04...glsl:510-713):
 // pop a ray, closest hit, surrounding RI, shadow rays, push reflect/refract, accumulate.
 // bunit: the lane's pixel unit when its primary ray may use the pixel's beam list (k_inw_pm), else kBeamOff
-// PK (walk parking, above): wp->resume continues a parked walk of this segment (its ray still
-// sits above K.size); wp->parked on return: the walk parked again and the segment is not done.
 // QN (k_inw_pm's GQ instance): the wide closest-hit walks read the quantised nodes (inw_closest)
-template <bool LIGHTS, bool LN = false, bool FU = false, bool PK = false, bool QN = false, class KS = FStack>
+template <bool LIGHTS, bool LN = false, bool FU = false, bool QN = false, class KS = FStack>
 __device__ void inw_segment(const InwScene &S, const Frame &F, KS &K, int s, f3 &color, float &depth, Ctr &c,
-                            uint32_t bunit = kBeamOff, WalkPark *wp = nullptr) {
-    static_assert(!PK || !QN, "walk parking keeps the segment's ray in the stack (FStack only)");
+                            uint32_t bunit = kBeamOff) {
     constexpr bool RLN = LN && !QN;  // the LBVH / RI walks' staged nodes (none in the GQ instance)
     const f3 D = mk(F.dir[0], F.dir[1], F.dir[2]);
     const float ratio = (float)s * F.inv_spp;
@@ -1426,19 +1423,11 @@ __device__ void inw_segment(const InwScene &S, const Frame &F, KS &K, int s, f3 
     unsigned long long t_tail = 0;  // the scatter and pushes after the RI (phase 7)
 #endif
     do {
-        const bool resumed = PK && wp->resume;
         f3 co, cd;
         float contribution, bounced;
-        if (!resumed) K.pop_ray(co, cd, contribution, bounced);
-        else {  // a parked walk: its ray still sits above K.size
-            const uint32_t b = K.size;
-            co = mk(K.at(b), K.at(b + 1), K.at(b + 2));
-            cd = mk(K.at(b + 3), K.at(b + 4), K.at(b + 5));
-            contribution = K.at(b + 6);
-            bounced = K.at(b + 7);
-        }
+        K.pop_ray(co, cd, contribution, bounced);
         bounced = (float)(int)bounced;
-        if (!resumed) c.seg++;
+        c.seg++;
         // SET LIMIT (01_BVH...glsl:424-428): a MULTIFOCUS primary ray stops at the lens
         const bool mf0 = !LIGHTS && F.n_focus > 0 && (int)(bounced + 0.1f) == 0;
         const float tlim0 = mf0 ? K.at(4) : kMaxT;
@@ -1448,14 +1437,12 @@ __device__ void inw_segment(const InwScene &S, const Frame &F, KS &K, int s, f3 
         INW_T0(t_ch);
         float fg;
         bool beam_ok = false;
-        if (!resumed && bunit != kBeamOff && (int)(bounced + 0.1f) == 0 && !mf0)  // a primary ray (pushed rays have bounced >= 1)
+        if (bunit != kBeamOff && (int)(bounced + 0.1f) == 0 && !mf0)  // a primary ray (pushed rays have bounced >= 1)
             fg = inw_closest_beam<true>(S, K, co, cd, ratio, invert, tlim, normal, extra, LIGHTS ? -1.0f : 0.0f, c, bunit,
                                         beam_ok);
-        if (!beam_ok) {
-            fg = inw_closest<true, LN, FU, PK, !LIGHTS, QN>(S, K, co, cd, ratio, invert, tlim, normal, extra,
-                                                            LIGHTS ? -1.0f : 0.0f, c, wp);
-            if (PK && wp->parked) return;  // the walk goes on in the next iteration
-        }
+        if (!beam_ok)
+            fg = inw_closest<true, LN, FU, !LIGHTS, QN>(S, K, co, cd, ratio, invert, tlim, normal, extra,
+                                                        LIGHTS ? -1.0f : 0.0f, c);
         INW_CYC(c, 0, t_ch);
         INW_T0(t_mat);
         const f3 hitpoint = co + cd * tlim;
@@ -1524,8 +1511,8 @@ __device__ void inw_segment(const InwScene &S, const Frame &F, KS &K, int s, f3 
                     f3 sd = normalize((bmin + (bmax - bmin) * ratio) - so);
                     c.shadow++;
                     f3 dummy_n; float dummy_e;
-                    float sg = inw_closest<false, LN, FU, false, !LIGHTS, QN>(S, K, so, sd, ratio, invert, sl, dummy_n,
-                                                                              dummy_e, -1.0f, c);
+                    float sg = inw_closest<false, LN, FU, !LIGHTS, QN>(S, K, so, sd, ratio, invert, sl, dummy_n,
+                                                                       dummy_e, -1.0f, c);
                     is_lit += (uint32_t)is_lit_geom(S, f2u(sg + 0.1f));
                 }
                 const uint32_t nl = S.n_lights > 1 ? S.n_lights : 1u;
@@ -2034,13 +2021,6 @@ __global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_
     UnitPix px{};
     uint32_t bu = kBeamOff;  // the lane's pixel unit for its beam list (S.beam)
     uint32_t pu = 0xffffffffu;  // the unit px and pcd belong to: a lane's next sample is mostly the same pixel's
-#ifdef RT_INW_PARK
-    constexpr bool PK = true;
-#else
-    constexpr bool PK = false;
-#endif
-    bool parked = false;  // PK: this lane's walk is parked (its segment resumes next iteration)
-    float4 *pslot = S.park ? S.park + 2 * ((size_t)blockIdx.x * blockDim.x + threadIdx.x) : nullptr;
     f3 pcd = f3{0, 0, 0};
     f3 col = f3{0, 0, 0};
     float dep = 0.0f;
@@ -2254,19 +2234,17 @@ __global__ __launch_bounds__((pm_sub<LN, GQ>() * kBlock)) __attribute__((amdgpu_
         constexpr int kRounds = LIGHTS ? 1 : 2;
 #pragma unroll 1
         for (int round = 2 - kRounds; round < 2; round++) {
-            const bool prim = bu != kBeamOff && !parked && K.top_primary();
-            const bool go = busy && (round == 0 ? prim : (parked || K.size > 0u));
+            const bool prim = bu != kBeamOff && K.top_primary();
+            const bool go = busy && (round == 0 ? prim : K.size > 0u);
             INW_T0(t_rnd);
             if (go) {
-                WalkPark wp{pslot, parked, false};
-                if (f.px_rays && !parked) atomicAdd(f.px_rays + px.out, 1u);  // rt_debug_pixel_rays (diagnostics only)
-                inw_segment<LIGHTS, WLN, FU, PK, GQ>(S, f, K, s, col, dep, c, bu, &wp);
-                parked = PK && wp.parked;
+                if (f.px_rays) atomicAdd(f.px_rays + px.out, 1u);  // rt_debug_pixel_rays (diagnostics only)
+                inw_segment<LIGHTS, WLN, FU, GQ>(S, f, K, s, col, dep, c, bu);
             }
 #ifdef RT_DIAG_SPLIT
             c.rnd[round] += (unsigned long long)clock64() - t_rnd;
 #endif
-            if (busy && !parked && K.size == 0) {  // sample done: its sqrt(colour) (01_BVH...glsl:670) to the ring
+            if (busy && K.size == 0) {  // sample done: its sqrt(colour) (01_BVH...glsl:670) to the ring
                 if constexpr (LR) {
                     const uint32_t e = g & rmask;
                     lr[RIX(0u, e)] = __builtin_sqrtf(col.x);

@@ -108,7 +108,6 @@ struct InwScene {
     uint32_t lring_sm = 0;    // k_inw_sm (768-lane instances): the same
     uint32_t xcdq = 0;        // k_inw_pm claims from per-XCD queues (rt_options.inw_claim_xcd)
     uint32_t ring_epoch = 0;  // fold-ring tags: the frame's epoch (0..62) << 26 (ring_tag, rt_kernels.hip)
-    float4 *park = nullptr;   // RT_INW_PARK builds: 2 float4 of parked walk state per lane of the fold grid
     // Quantised wide nodes (DESIGN.md §5.2 "Quantised nodes"; null = off): the culling BVH of
     // wnodes as 4 float4 per node -- origin.xyz, scale.x | scale.yz, low-plane bytes x, y | low z,
     // high x, y, z (byte k = child k) | links -- each plane rounded outward (rt_build.hip:
