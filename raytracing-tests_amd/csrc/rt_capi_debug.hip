@@ -1,0 +1,296 @@
+// rt_capi_debug.hip -- the rt_debug_* entry points of include/rt_hip_debug.h: diagnostics and
+// what the tests ask about the last render.  No exception crosses the ABI.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "rt_dev_scene.hpp"
+
+unsigned long long *g_dbg = nullptr;
+unsigned *g_px_rays = nullptr;
+bool g_time_kernels = false;
+
+namespace {
+
+// a histogram of n u64 over the scene's sample-parallel records: zeroed, filled by fn on the
+// device, copied to out
+template <class F> int spec_hist_out(rt_dev_scene *s, uint64_t *out, size_t n, F &&fn) {
+    if (!s || !out) return RT_E_ARG;
+    std::memset(out, 0, n * sizeof(uint64_t));
+    if (!s->sp.cap) return RT_OK;
+    DevBuf d;
+    HIP_OK(d.alloc(n * sizeof(uint64_t)));
+    HIP_OK(hipMemset(d.p, 0, n * sizeof(uint64_t)));
+    HIP_OK(fn(d.as<unsigned long long>()));
+    HIP_OK(hipMemcpy(out, d.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_debug_build_level_cap(int levels) {
+    if (levels < 0) return RT_E_ARG;
+    g_build_levels = levels;
+    return RT_OK;
+}
+
+int rt_debug_wide_info(rt_dev_scene *s, uint32_t info[8], uint32_t *rank_out) {
+    if (!s || s->kind == 3 || !info) return RT_E_ARG;
+    HIP_OK(hipSetDevice(s->device));
+    HIP_OK(hipDeviceSynchronize());
+    const InwWalk &w = s->walk;
+    const uint32_t cells = w.ri_ok ? uint32_t(w.ri_dim[0]) * uint32_t(w.ri_dim[1]) * uint32_t(w.ri_dim[2]) : 0u;
+    const uint32_t v[8] = {w.n_wtree0, w.dfs_high, uint32_t(w.wdepth), w.ri_ok ? 1u : 0u, cells,
+                           w.sl_ok ? 1u : 0u, s->n, w.wbuild};
+    std::memcpy(info, v, sizeof(v));
+    if (rank_out && w.n_wnodes)
+        HIP_OK(hipMemcpy(rank_out, w.wrank.p, size_t(s->n) * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_debug_path(rt_dev_scene *s, rt_path_info *out) {
+    if (!s || !out) return RT_E_ARG;
+    char name[64] = {0};
+    const int n = rt_debug_launches(s, name, int(sizeof(name)));  // resolves the fold kernel (synchronises)
+    if (n < 0) return n;
+    const LastRender &L = s->last;
+    const uint32_t n_wtree0 = s->walk.n_wtree0;
+    rt_path_info P = L.path;
+    std::memcpy(P.kernel, name, sizeof(P.kernel));
+    P.launches = n;
+    P.ref_walks = 0;
+    if (s->kind != 3 && s->walk_ctr.p) {
+        unsigned long long v = 0;
+        HIP_OK(hipMemcpy(&v, s->walk_ctr.p, sizeof(v), hipMemcpyDeviceToHost));
+        P.ref_walks = v;
+    }
+    if (std::strncmp(name, "k_inw_pm", 8) == 0) {
+        P.order = 1;
+        P.ring_entries = int(L.ring[0]);
+        P.ring_lds = L.lring ? 1 : 0;
+        if (L.lring && !L.gq) { P.lds_nodes = 0; P.lbvh_lds_nodes = 0; }  // the FStack ring instances stage no nodes
+        if (L.ln && !L.lring) P.time_bins = 0;  // the global-ring LN instance walks the staged swept tree
+    }
+    else if (std::strncmp(name, "k_inw_sm", 8) == 0) {
+        P.order = 2;
+        P.ring_entries = int(L.ring[1]);
+        P.ring_lds = L.lring_sm ? 1 : 0;
+        if (L.lring_sm) P.lds_nodes = std::min(P.lds_nodes, int(rtk::kPmLdsNodes));
+        if (L.lring_sm) P.lbvh_lds_nodes = std::min(P.lbvh_lds_nodes, int(rtk::kPmLdsNodes * 10 / 2));
+        if (L.ln) P.time_bins = 0;  // its walks read the staged top of the swept tree
+        if (L.gq) {  // the GQ instance is pixel-major only: k_inw_sm ran the 236-node FStack kernel
+            P.qnodes = 0; P.global_stack = 0; P.walk_stack = rtk::kFStack - 3;
+            P.lds_nodes = L.lring_sm ? std::min(n_wtree0, rtk::kPmLdsNodes) : std::min(n_wtree0, uint32_t(rtk::kInwLdsNodes));
+        }
+    }
+    if (P.order != 1) { P.beams = 0; P.claim_order = 0; P.beam_bins = 0; }  // both serve the pixel-major kernel only
+    *out = P;
+    return RT_OK;
+}
+
+// Diagnostics (not part of the reference's surface): pass a device buffer of 8 u64 to make
+// the kernels tally lane occupancy per phase; NULL turns it off.
+int rt_debug_counters(uint64_t *d_buf) {
+    g_dbg = reinterpret_cast<unsigned long long *>(d_buf);
+    return RT_OK;
+}
+
+int rt_debug_pixel_rays(uint32_t *d_buf) {
+    g_px_rays = d_buf;
+    return RT_OK;
+}
+
+int rt_debug_rounds(rt_dev_scene *s, uint32_t *out, int cap) {
+    if (!s || !out || cap <= 0) return RT_E_ARG;
+    if (!s->ws.cont_count.p) return 0;
+    std::vector<unsigned> v(16 * 16);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(v.data(), s->ws.cont_count.p, v.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    const int n = std::min(cap, 16);
+    for (int r = 0; r < n; r++) out[r] = v[size_t(16) * r];
+    return n;
+}
+
+int rt_debug_spec_hist(rt_dev_scene *s, uint64_t *out) {
+    return spec_hist_out(s, out, 66, [&](unsigned long long *d) {
+        return rtk::spec_hist(s->sp.ctr.as<uint4>(), s->sp.cap, d, nullptr);
+    });
+}
+
+int rt_debug_spec_list_hist(rt_dev_scene *s, uint64_t *out) {
+    return spec_hist_out(s, out, 66, [&](unsigned long long *d) {
+        return rtk::spec_list_hist(s->sp.ctr.as<uint4>(), s->sp.P, s->sp.S, s->sp.list.as<uint32_t>(),
+                                   s->sp.counts.as<unsigned>(), d, nullptr);
+    });
+}
+
+int rt_debug_spec_list_stale(rt_dev_scene *s, uint64_t *out) {
+    return spec_hist_out(s, out, 32, [&](unsigned long long *d) {
+        return rtk::spec_list_stale(s->sp.ctr.as<uint4>(), s->sp.P, s->sp.S, s->sp.list.as<uint32_t>(),
+                                    s->sp.counts.as<unsigned>(), d, nullptr);
+    });
+}
+
+int rt_debug_spec_pixels(rt_dev_scene *s, uint32_t *out, uint32_t cap_units) {
+    if (!s || !out) return RT_E_ARG;
+    if (!s->sp.cap || !s->sp.P || s->sp.P > cap_units) return RT_E_ARG;
+    const uint32_t P = s->sp.P, S = s->sp.S;  // the last render's record layout
+    DevBuf d;
+    HIP_OK(d.alloc(size_t(P) * 16));
+    HIP_OK(rtk::spec_pixels(s->sp.ctr.as<uint4>(), P, S, s->ws.order.as<uint32_t>(), d.as<uint32_t>(), nullptr));
+    HIP_OK(hipMemcpy(out, d.p, size_t(P) * 16, hipMemcpyDeviceToHost));
+    return int(P);
+}
+
+int rt_debug_spec_dump(rt_dev_scene *s, uint32_t *rays_out, size_t cap, uint32_t *list_out, uint32_t list_cap,
+                       uint32_t *dims) {
+    if (!s || !rays_out || !dims) return RT_E_ARG;
+    if (!s->sp.cap || !s->sp.P) return RT_E_ARG;
+    const uint32_t P = s->sp.P, S = s->sp.S;  // the last render's record layout (SpecRecs::ix)
+    if (size_t(P) * S > cap) return RT_E_ARG;
+    std::vector<uint4> h(size_t(P) * S);
+    HIP_OK(hipMemcpy(h.data(), s->sp.ctr.p, h.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+    for (size_t u = 0; u < h.size(); u++) rays_out[u] = h[rtk::spec_rec_ix(u, P, S)].x;  // in unit order s * P + pu
+    unsigned cnt[32] = {};
+    HIP_OK(hipMemcpy(cnt, s->sp.counts.p, sizeof(cnt), hipMemcpyDeviceToHost));
+    const uint32_t nl = std::min(cnt[0], list_cap);
+    if (list_out && nl) HIP_OK(hipMemcpy(list_out, s->sp.list.p, size_t(nl) * 4, hipMemcpyDeviceToHost));
+    dims[0] = P; dims[1] = S; dims[2] = cnt[0]; dims[3] = cnt[16];
+    return RT_OK;
+}
+
+int rt_debug_spec_times(rt_dev_scene *s, uint32_t *start_out, uint32_t *end_out, size_t cap) {
+    if (!s || !start_out || !end_out || !s->sp.dbg_n || !s->sp.dbg_t.p) return RT_E_ARG;
+    const size_t n = s->sp.dbg_n;  // the last render's P * S: its end times start at offset n
+    if (n > cap || s->sp.dbg_t.bytes < 2 * n * sizeof(uint32_t)) return RT_E_ARG;
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(start_out, s->sp.dbg_t.p, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(end_out, static_cast<char *>(s->sp.dbg_t.p) + n * 4, n * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_debug_launches(rt_dev_scene *s, char *name_out, int name_cap) {
+    if (!s) return RT_E_ARG;
+    LastRender &L = s->last;
+    if (L.fold_pending) {
+        // the probe picked the fold kernel on the device: read its verdict (synchronises)
+        uint32_t m[2] = {0, 0};
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipMemcpy(m, s->fold.mode.p, sizeof(m), hipMemcpyDeviceToHost));
+        const uint32_t ord = L.force;  // the order the launch used (0: the probe's verdict)
+        const bool sm = ord == 2 || (ord != 1 && m[0] > 0 && 2 * m[1] >= m[0]);
+        // the template instance's name as rocprofv3 prints it, every template argument:
+        // <LIGHTS, LN (LDS-staged BVH top), FU (fused cull), LRING (the fold ring in LDS)[, GQ (k_inw_pm)]>
+        auto tf = [](bool b) { return b ? "true" : "false"; };
+        const bool lights = s->layout == 4;
+        if (sm)
+            std::snprintf(L.kernel, sizeof(L.kernel), "k_inw_sm<%s, %s, %s, %s>", tf(lights), tf(L.ln), tf(L.fu),
+                          tf(L.lring_sm));
+        else
+            std::snprintf(L.kernel, sizeof(L.kernel), "k_inw_pm<%s, %s, %s, %s, %s>", tf(lights), tf(L.ln), tf(L.fu),
+                          tf(L.lring || L.gq), tf(L.gq));
+        L.fold_pending = false;
+    }
+    if (name_out && name_cap > 0) {
+        std::strncpy(name_out, L.kernel, size_t(name_cap) - 1);
+        name_out[name_cap - 1] = 0;
+    }
+    return L.launches;
+}
+
+int rt_debug_chunks(rt_dev_scene *s) {
+    if (!s) return RT_E_ARG;
+    return s->last.chunks;
+}
+
+int rt_debug_check_fastmath(int which, uint64_t *mismatches, uint32_t *first_bad) {
+    if (!mismatches || !first_bad || which != 0) return RT_E_ARG;
+    DevBuf d;
+    HIP_OK(d.alloc(16));
+    HIP_OK(hipMemset(d.p, 0, 8));
+    HIP_OK(hipMemset(static_cast<char *>(d.p) + 8, 0xff, 4));
+    HIP_OK(rtk::launch_check_fastmath(which, d.as<unsigned long long>(), reinterpret_cast<unsigned *>(static_cast<char *>(d.p) + 8),
+                                 nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(mismatches, d.p, 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(first_bad, static_cast<char *>(d.p) + 8, 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_debug_time_kernels(int on) {
+    g_time_kernels = on != 0;
+    return RT_OK;
+}
+
+int rt_debug_kernel_time(rt_dev_scene *s, double *ms_total, int *launches) {
+    if (!s || !ms_total || !launches) return RT_E_ARG;
+    double t = 0.0;
+    for (size_t i = 0; i < s->kt_used; i++) {
+        HIP_OK(hipEventSynchronize(s->kt_ev[i].second));
+        float ms = 0.0f;
+        HIP_OK(hipEventElapsedTime(&ms, s->kt_ev[i].first, s->kt_ev[i].second));
+        t += ms;
+    }
+    *ms_total = t;
+    *launches = int(s->kt_used);
+    return RT_OK;
+}
+
+int rt_debug_time_bins(const float *nodes, const float *geom, uint32_t n, uint32_t bins, float *wnodes_out,
+                       uint32_t wnodes_cap, uint32_t info[4]) {
+    if (!nodes || !geom || n == 0 || !info) return RT_E_ARG;
+    try {
+        rtamd::InwWide w;
+        if (!rtamd::inw_wide_build(nodes, n, w)) { std::memset(info, 0, 4 * sizeof(uint32_t)); return RT_OK; }
+        rtamd::inw_wide_add_bins(geom, n, bins, w);
+        const uint32_t total = uint32_t(w.wnodes.size() / 40);
+        const uint32_t v[4] = {w.n_tree0, w.bins, w.bin_stride, total};
+        std::memcpy(info, v, sizeof(v));
+        if (wnodes_out && wnodes_cap >= total) std::memcpy(wnodes_out, w.wnodes.data(), w.wnodes.size() * sizeof(float));
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_debug_bin_boxes(const float *geom, uint32_t n, uint32_t bins, uint32_t b, float *boxes_out) {
+    if (!geom || !boxes_out || n == 0 || bins == 0 || b >= bins) return RT_E_ARG;
+    try {
+        std::vector<float> boxes;
+        float wb = 0.0f;
+        if (!rtamd::inw_bin_boxes(geom, n, bins, b, boxes, wb)) return RT_E_ARG;
+        std::memcpy(boxes_out, boxes.data(), boxes.size() * sizeof(float));
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_debug_sphere_records(const float *geom, uint32_t n, int layout, float *out) {
+    if (!geom || !out || n == 0 || (layout != 1 && layout != 4)) return RT_E_ARG;
+    try {
+        std::vector<float> r;
+        if (!inw_sphere_records(geom, n, layout, r)) return 0;
+        std::memcpy(out, r.data(), r.size() * sizeof(float));
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    return 1;
+}
+
+int rt_debug_trace_kernel(int any, int fused, int info[4]) {
+    if (!info) return RT_E_ARG;
+    HIP_OK(rtk::inw_trace_kernel_info(any != 0, fused != 0, info));
+    return RT_OK;
+}
+
+int rt_debug_trace_iow_kernel(int any, int lds, int info[4]) {
+    if (!info) return RT_E_ARG;
+    HIP_OK(rtk::iow_trace_kernel_info(any != 0, lds != 0, info));
+    return RT_OK;
+}
+
+}  // extern "C"

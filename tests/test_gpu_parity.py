@@ -375,3 +375,99 @@ def test_iow03_tile_after_full_frame_uses_its_own_records(gpu):
         g, _, gst = R.render(sc, p)
         assert compare(g[sl], o[sl])["exact_frac"] == 1.0
         assert gst["segments"] == ost["segments"], (gst["segments"], ost["segments"])
+
+
+def test_render_at_once_on_a_non_blocking_stream(gpu):
+    """A scene handed back by rt_dev_scene_inw, or updated by rt_dev_scene_inw_update with the
+    caller's host LBVH, is complete: its derived nodes (the compacted culling BVH the wide walks
+    read, written by kernels on the null stream) are finished before the call returns.  So a render
+    enqueued at once on a fresh non-blocking stream, with only that stream synchronised, is
+    bit-identical to the oracle in colour and depth with the same ray count, and rt_debug_path
+    reports the wide walk, i.e. those nodes were in fact read.
+
+    What this can and cannot do: it pins the contract, and catches a change that reorders the
+    work (a render that starts before the nodes' kernels, or skips them).  A race that happens to
+    be won does not fail it: without the wait the two small kernels usually finish first anyway."""
+    import ctypes as C
+
+    import torch
+
+    a = R.make_scene(R.PRESET_INW01_RANDOM, 1234, 3000, width=64, height=36, spp=8)
+    b = R.make_scene(R.PRESET_INW01_RANDOM, 1234, 3000, width=64, height=36, spp=8)
+    for i in range(b.n):  # every object moves
+        for k in range(3):
+            b.desc[i].position[k] += 0.25 * ((i + k) % 3 - 1)
+    for k, v in R.pack(b.desc, b.n, b.stage).items():
+        setattr(b, k, v)
+    lib = R.load()
+    dev = torch.device("cuda")
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):  # the outputs of both frames, cleared on the render's stream
+        out = [(torch.zeros((36, 64, 4), dtype=torch.float32, device=dev),
+                torch.zeros((36, 64), dtype=torch.float32, device=dev),
+                torch.zeros(6, dtype=torch.int64, device=dev)) for _ in range(2)]
+
+    def frame(s, sc, bufs):
+        img, dep, ctr = bufs
+        assert lib.rt_render_image_async(s, C.byref(sc.camera), C.byref(sc.params), img.data_ptr(), dep.data_ptr(),
+                                         ctr.data_ptr(), st.cuda_stream) == 0
+        st.synchronize()  # that stream only
+        path = R.debug_path(s)
+        with torch.cuda.stream(st):
+            return img.cpu().numpy(), dep.cpu().numpy(), int(ctr[0].item()), path
+
+    s = lib.rt_dev_scene_inw(R.fptr(a.geom), a.n, 1, R.fptr(a.nodes), None, 0, a.params.spp, -1)
+    assert s
+    try:
+        fa = frame(s, a, out[0])
+        tm = (C.c_double * 4)()
+        assert lib.rt_dev_scene_inw_update(s, R.fptr(b.geom), b.n, R.fptr(b.nodes), R.fptr(b.aabbs), None, 0, tm) == 0
+        fb = frame(s, b, out[1])
+    finally:
+        lib.rt_dev_scene_free(s)
+    for sc, (g, gd, gs, path) in ((a, fa), (b, fb)):
+        o, od, ost = O.render(sc)
+        assert path["wide_walk"] == 1, path
+        assert compare(g, o)["exact_frac"] == 1.0 and compare(gd, od)["exact_frac"] == 1.0
+        assert gs == ost["segments"], (gs, ost["segments"])
+
+
+def test_iow03_workspaces_regrow_with_the_frame_size(gpu):
+    """One IOW-03 device scene renders 32x24, then 48x32, then 32x24 again: at the second frame its
+    per-frame-size buffers are dropped and allocated anew -- by default the sample-parallel records,
+    the chunk workspace and the pipeline's sort scratch, with iow_spec = 0 and iow_chunks_lpt = 1
+    (spp 4: four chunks) the chunk workspace and the per-pixel chunk state -- and the third frame
+    runs in the larger buffers.  Every frame is bit-identical to the oracle's render at its size,
+    with the same ray count."""
+    import ctypes as C
+
+    import torch
+
+    sizes = ((32, 24), (48, 32), (32, 24))
+    scs = {wh: R.make_scene(R.PRESET_IOW03_FINAL, 20250131, 0, width=wh[0], height=wh[1], spp=4) for wh in set(sizes)}
+    refs = {wh: O.render(sc) for wh, sc in scs.items()}
+    lib = R.load()
+    dev = torch.device("cuda")
+    for over in ({}, {"iow_spec": 0, "iow_chunks_lpt": 1}):
+        sc0 = scs[sizes[0]]
+        s = lib.rt_dev_scene_iow03(R.fptr(sc0.types), R.fptr(sc0.records), sc0.n, 4, -1)
+        assert s
+        try:
+            o = R.default_options()
+            for k, v in over.items():
+                setattr(o, k, v)
+            assert lib.rt_dev_scene_set_options(s, C.byref(o)) == 0
+            for i, (w, h) in enumerate(sizes):
+                sc = scs[(w, h)]
+                img = torch.zeros((h, w, 4), dtype=torch.float32, device=dev)
+                ctr = torch.zeros(6, dtype=torch.int64, device=dev)
+                assert lib.rt_render_image_async(s, C.byref(sc.camera), C.byref(sc.params), img.data_ptr(), None,
+                                                 ctr.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
+                torch.cuda.synchronize()
+                if over:
+                    assert lib.rt_debug_chunks(s) == 4
+                ref, _, rst = refs[(w, h)]
+                assert compare(img.cpu().numpy(), ref)["exact_frac"] == 1.0, (over, i)
+                assert int(ctr[0].item()) == rst["segments"], (over, i)
+        finally:
+            lib.rt_dev_scene_free(s)
