@@ -414,6 +414,55 @@ int rt_trace_iow_rays_async(rt_dev_scene *s, const rt_ray *d_rays, uint32_t n_ra
 int rt_trace_iow03(const float *types, const float *records /* N*24 */, uint32_t n, const rt_ray *rays,
                    uint32_t n_rays, int flags, rt_hit *hits, int device, rt_stats *st);
 
+/* ---- path (radiance) queries --------------------------------------------------------------
+ * Batched path queries on an INW device scene: what does this ray SEE?  (Light probes, reflection
+ * captures, "why is sample 37 of this pixel white?".)  One query is one invocation of the reference
+ * shader's out_Pixel ray loop -- layout 1: 01_BoundingVolumeHierarchy/computeShaderSrc.glsl:414-597;
+ * layout 4: 04_Lights_Camera_And_Action/computeShaderSrc.glsl:510-713 -- started from the caller's
+ * ray instead of the camera's: an empty 40-float stack, push_ray(o, d, contribution = 1,
+ * bounced = 0), no MULTIFOCUS record, then the loop to its end with the materials and textures,
+ * the surrounding-RI walks, INW-04's shadow rays, the scatter step and the stack's silent drops.
+ * For the shader's own camera ray of (pixel, sample s) a query returns exactly that sample's
+ * `color` and `depth`, so a frame is the End() fold of path queries, bit for bit.  The kernel runs
+ * the render path's own segment (the scene's options apply), so results are bit-identical whatever
+ * the options.
+ *   - sample = the shader's sample index s: the time ratio is (float)s * (1.0f / spp) and the
+ *     scatter offsets are sunflower[2s], [2s + 1] of the scene's table; spp is the value the scene
+ *     was created with.  u_NumOfBounces = max_bounces.  pad is ignored: any bits may be in it.
+ *   - The primary ray's limit is the shader's 32000; there is no per-ray tmax.
+ *   - RT_TRACE_INVERT selects the child order of the walks, as for rt_trace_rays_async.  Any other
+ *     flag bit is an error.
+ *   - rgb = the loop's final `color`: before End()'s sqrt, and (1, 1, 1) after INW-04's
+ *     lit-geometry break.
+ *   - depth = the shader's `depth`.  It is written only by a segment that MISSES, so it is 0 or that
+ *     miss's t_limiting (32000 for a primary miss): the shader's behaviour, not a hit distance --
+ *     rt_trace_rays_async answers that.
+ *   - segments, drops, nans = this path's rays popped, pushes the full stack dropped and NaN
+ *     secondary directions; status = 0.
+ *   - sample >= spp: status = 1 and every other field 0; no path runs and the query is not counted.
+ *   - counters (6 x u64 as rt_stats' first six fields, added to): [0] += segments, [3] += shadow
+ *     queries, [4] += dropped pushes, [5] += NaN directions, all as the reference counts them;
+ *     [1], [2] this build's own node visits and primitive tests (they depend on the options and on
+ *     the skipped RI walks, as in the renders).
+ * Returns RT_E_ARG for a null scene, null rays or out with n_rays > 0, a flag bit other than
+ * RT_TRACE_INVERT, max_bounces < 0, n_rays > 2^31 or a scene a failed update left broken;
+ * RT_E_UNSUPPORTED for an IOW-03 scene: an IOW-03 sample reads the RI stack the previous sample of
+ * its pixel left behind, so a single ray has no defined radiance there.  n_rays == 0 returns RT_OK
+ * and launches nothing.  Every argument error comes back before a device is touched.  Calls on one
+ * scene must not overlap each other, its renders or its ray queries (they share its work queue). */
+typedef struct rt_path_ray { float o[3]; uint32_t sample; float d[3]; uint32_t pad; } rt_path_ray;   /* 32 B */
+typedef struct rt_path_out { float rgb[3]; float depth; uint32_t segments, drops, nans, status; } rt_path_out; /* 32 B */
+/* Device pointers (16-byte aligned); never allocates or synchronises. */
+int rt_path_rays_async(rt_dev_scene *s, const rt_path_ray *d_rays, uint32_t n_rays, int max_bounces, int flags,
+                       rt_path_out *d_out, uint64_t *d_counters /* 6 x u64, added to; may be NULL */, void *stream);
+/* Blocking: host buffers; builds a device scene for the call like rt_render_inw_tex (sample tables
+ * of `spp` entries, lights, textures).  st (may be NULL): the counters and the kernel's device time.
+ * RT_E_ARG also for null geom / nodes, n == 0, a layout other than 1 and 4, spp < 1, n_lights > 0
+ * with null lights or bad textures; RT_E_UNSUPPORTED for textured objects with no texture bound. */
+int rt_path_inw(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights, uint32_t n_lights,
+                const rt_texture *tex, int n_tex, int spp, int max_bounces, const rt_path_ray *rays, uint32_t n_rays,
+                int flags, rt_path_out *out, int device, rt_stats *st);
+
 /* ---- multi-GPU partition (BASELINE configs[3]) -----------------------------
  * One host thread drives several devices of this process: the frame's tiles are dealt
  * across the devices, each renders its share with rt_render_tiles_async on a stream of its own,

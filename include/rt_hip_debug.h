@@ -128,6 +128,12 @@ int rt_debug_trace_kernel(int any, int fused, int info[4]);
 /* The same for the IOW-03 ray-query kernel (rt_trace_iow_rays_async): lds = 1 the instance with
  * the BVH staged in LDS, 0 the one that reads nodes from global memory (also the linear loop's). */
 int rt_debug_trace_iow_kernel(int any, int lds, int info[4]);
+/* The same for the path-query kernel (rt_path_rays_async): lights = 1 the INW-04 instance, 0 the
+ * INW-01 one, with the fused cull or without. */
+int rt_debug_paths_kernel(int lights, int fused, int info[4]);
+/* Caps the path-query kernel's grid at `blocks` 256-lane blocks (0 = the default, the resident
+ * grid), so that a test can make one block answer many queries.  Returns the previous cap. */
+int rt_debug_paths_max_blocks(int blocks);
 
 #ifdef __cplusplus
 }

@@ -76,11 +76,13 @@ int render_temp(const rt_camera *cam, const rt_params *p, float *rgba, float *de
     return render_blocking(s.get(), cam, p, rgba, depth, st);
 }
 
-// The blocking ray queries: a temporary scene from make(scene), the rays up, trace(scene, rays,
-// hits, counters) timed on the null stream, the hits and the counters back.
-template <class Make, class Trace>
-int trace_blocking(int flags, int allowed, const rt_ray *rays, uint32_t n_rays, rt_hit *hits, int device, rt_stats *st,
+// The blocking ray and path queries: a temporary scene from make(scene), the rays up, trace(scene,
+// rays, hits, counters) timed on the null stream, the hits and the counters back.  Ray / Hit: the
+// 32-byte query and answer records (rt_ray / rt_hit, rt_path_ray / rt_path_out).
+template <class Ray, class Hit, class Make, class Trace>
+int trace_blocking(int flags, int allowed, const Ray *rays, uint32_t n_rays, Hit *hits, int device, rt_stats *st,
                    Make &&make, Trace &&trace) {
+    static_assert(sizeof(Ray) == 32 && sizeof(Hit) == 32, "queries and answers are 2 float4 each");
     if ((flags & ~allowed) || n_rays > (1u << 31)) return RT_E_ARG;
     if (n_rays > 0 && (!rays || !hits)) return RT_E_ARG;
     int rc = check_device(device);
@@ -96,14 +98,14 @@ int trace_blocking(int flags, int allowed, const rt_ray *rays, uint32_t n_rays, 
     if (st) std::memset(st, 0, sizeof(*st));
     if (n_rays == 0) return RT_OK;
     DevBuf d_rays, d_hits, d_ctr;
-    const size_t bytes = size_t(n_rays) * sizeof(rt_ray);
+    const size_t bytes = size_t(n_rays) * sizeof(Ray);
     HIP_OK(d_rays.alloc(bytes));
     HIP_OK(d_hits.alloc(bytes));
     HIP_OK(d_ctr.alloc(6 * sizeof(unsigned long long)));
     HIP_OK(hipMemcpy(d_rays.p, rays, bytes, hipMemcpyHostToDevice));
     HIP_OK(hipMemset(d_ctr.p, 0, 6 * sizeof(unsigned long long)));
     double ms = 0.0;
-    rc = timed([&] { return trace(s.get(), d_rays.as<rt_ray>(), d_hits.as<rt_hit>(), d_ctr.as<uint64_t>()); }, &ms);
+    rc = timed([&] { return trace(s.get(), d_rays.as<Ray>(), d_hits.as<Hit>(), d_ctr.as<uint64_t>()); }, &ms);
     if (rc != RT_OK) return rc;
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(hits, d_hits.p, bytes, hipMemcpyDeviceToHost));
@@ -527,6 +529,48 @@ int rt_trace_iow03(const float *types, const float *records, uint32_t n, const r
         [&](rt_dev_scene *s) { return make_iow03(s, types, records, n, 1); },  // spp = 1: the sample tables are unused
         [&](rt_dev_scene *s, const rt_ray *d_rays, rt_hit *d_hits, uint64_t *d_ctr) {
             return rt_trace_iow_rays_async(s, d_rays, n_rays, flags, d_hits, d_ctr, nullptr);
+        });
+}
+
+// ------------------------------------------------------------------------ path queries
+int rt_path_rays_async(rt_dev_scene *s, const rt_path_ray *d_rays, uint32_t n_rays, int max_bounces, int flags,
+                       rt_path_out *d_out, uint64_t *d_counters, void *stream) {
+    static_assert(sizeof(rt_path_ray) == 32 && sizeof(rt_path_out) == 32, "rt_path_ray / rt_path_out are 2 float4 each");
+    if (!s || (flags & ~RT_TRACE_INVERT) || max_bounces < 0) return RT_E_ARG;
+    if (s->kind == 3) return RT_E_UNSUPPORTED;  // an IOW-03 sample starts from its pixel's previous one
+    if (s->broken || n_rays > (1u << 31)) return RT_E_ARG;
+    if (n_rays == 0) return RT_OK;
+    if (!d_rays || !d_out) return RT_E_ARG;
+    rtk::InwScene sc = inw_view(*s);
+    // as in the renders and rt_trace_rays_async: only layout-1 walks read the sphere records, and the
+    // fused cull needs the scene's culling boxes within 1000 of the origin (the kernel checks each
+    // query's origin)
+    if (s->layout == 4) sc.sph = nullptr;
+    sc.fused = (s->opt.inw_fused_cull && sc.wnodes && s->walk.wbound <= 1000.0f) ? 1 : 0;
+    // its own queue counter: clear of the fold kernels' (bytes 0..767) and the ray queries' (word 240)
+    unsigned *queue = s->counter.as<unsigned>() + 224;
+    const hipError_t e = rtk::launch_inw_paths(sc, reinterpret_cast<const float4 *>(d_rays), n_rays, s->spp,
+                                               max_bounces, (flags & RT_TRACE_INVERT) != 0,
+                                               reinterpret_cast<float4 *>(d_out),
+                                               reinterpret_cast<unsigned long long *>(d_counters), queue, s->cus,
+                                               static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RT_OK : launch_failed(e);
+}
+
+int rt_path_inw(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights, uint32_t n_lights,
+                const rt_texture *tex, int n_tex, int spp, int max_bounces, const rt_path_ray *rays, uint32_t n_rays,
+                int flags, rt_path_out *out, int device, rt_stats *st) {
+    if (!geom || !nodes || n == 0 || (layout != 1 && layout != 4) || spp < 1 || max_bounces < 0) return RT_E_ARG;
+    if (layout == 4 && n_lights > 0 && !lights) return RT_E_ARG;
+    if (!textures_ok(tex, n_tex)) return RT_E_ARG;
+    if ((flags & ~RT_TRACE_INVERT) || n_rays > (1u << 31) || (n_rays > 0 && (!rays || !out))) return RT_E_ARG;
+    if (n_tex == 0 && inw_textured(geom, n, layout)) return RT_E_UNSUPPORTED;  // no texture bound
+    return trace_blocking(
+        flags, RT_TRACE_INVERT, rays, n_rays, out, device, st,
+        // the scene of rt_render_inw_tex: the sunflower table is spp long
+        [&](rt_dev_scene *s) { return make_inw(s, geom, n, layout, nodes, lights, n_lights, tex, n_tex, spp); },
+        [&](rt_dev_scene *s, const rt_path_ray *d_rays, rt_path_out *d_out, uint64_t *d_ctr) {
+            return rt_path_rays_async(s, d_rays, n_rays, max_bounces, flags, d_out, d_ctr, nullptr);
         });
 }
 

@@ -293,4 +293,12 @@ int rt_debug_trace_iow_kernel(int any, int lds, int info[4]) {
     return RT_OK;
 }
 
+int rt_debug_paths_kernel(int lights, int fused, int info[4]) {
+    if (!info) return RT_E_ARG;
+    HIP_OK(rtk::inw_paths_kernel_info(lights != 0, fused != 0, info));
+    return RT_OK;
+}
+
+int rt_debug_paths_max_blocks(int blocks) { return rtk::inw_paths_max_blocks(blocks); }
+
 }  // extern "C"

@@ -418,6 +418,17 @@ hipError_t launch_iow_trace(const IowScene &sc, int leaf_batch, const float4 *ra
 int iow_trace_blocks_per_cu(bool any, bool ln);
 // k_iow_trace's {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} (hipFuncGetAttributes)
 hipError_t iow_trace_kernel_info(bool any, bool ln, int info[4]);
+// rt_paths.hip: n_rays path queries (rt_path_ray / rt_path_out as 2 float4 each) on a persistent grid
+// of at most cus * inw_paths_blocks_per_cu blocks with persistent lanes; queue: one u32 (zeroed
+// here); counters: 6 x u64 added to, or null.  sc.layout picks INW-01 / INW-04, sc.fused the
+// fused-cull instance; spp: the length of sc.sunflower / 2.
+hipError_t launch_inw_paths(const InwScene &sc, const float4 *rays, uint32_t n_rays, int spp, int max_bounces,
+                            bool invert, float4 *out, unsigned long long *counters, unsigned *queue, int cus,
+                            hipStream_t s);
+int inw_paths_blocks_per_cu(bool lights, bool fused);
+// k_inw_paths' {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} (hipFuncGetAttributes)
+hipError_t inw_paths_kernel_info(bool lights, bool fused, int info[4]);
+int inw_paths_max_blocks(int blocks);  // rt_debug_paths_max_blocks: cap the grid (0 = off); the previous cap
 // resident blocks per CU of the render kernel for `kind` (3 = IOW-03 wide, 4 = IOW-03 narrow,
 // 11/14 = INW layout 1/4)
 int resident_blocks_per_cu(int kind);  // 5 = sample-parallel IOW-03, 6/7 = sample-parallel INW 1/4,

@@ -201,6 +201,12 @@ SIGNATURES = {
     "rt_trace_iow03": (C.c_int, [_FP, _FP, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int,
                                  C.POINTER(RtStats)]),
     "rt_debug_trace_iow_kernel": (C.c_int, [C.c_int, C.c_int, _IP]),
+    "rt_path_rays_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "rt_path_inw": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtTexture), C.c_int, C.c_int,
+                              C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.POINTER(RtStats)]),
+    "rt_debug_paths_kernel": (C.c_int, [C.c_int, C.c_int, _IP]),
+    "rt_debug_paths_max_blocks": (C.c_int, [C.c_int]),
     "rt_render_multi_async": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
@@ -556,6 +562,37 @@ def trace_iow_kernel_info(any_hit: bool = False, lds: bool = True) -> dict:
     """rt_debug_trace_iow_kernel: the IOW-03 query kernel's registers, scratch, LDS and resident blocks per CU."""
     info = (C.c_int * 4)()
     check(load().rt_debug_trace_iow_kernel(int(any_hit), int(lds), info), "rt_debug_trace_iow_kernel")
+    return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
+
+
+# --------------------------------------------------------------------- path queries
+# rt_path_ray / rt_path_out (include/rt_hip.h), 32 bytes each
+PATH_RAY_DTYPE = np.dtype([("o", np.float32, 3), ("sample", np.uint32), ("d", np.float32, 3), ("pad", np.uint32)])
+PATH_OUT_DTYPE = np.dtype([("rgb", np.float32, 3), ("depth", np.float32), ("segments", np.uint32),
+                           ("drops", np.uint32), ("nans", np.uint32), ("status", np.uint32)])
+
+
+def paths(sc: Scene, rays: np.ndarray, max_bounces: int, flags: int = 0, device: int = -1):
+    """rt_path_inw: blocking path (radiance) queries of `rays` (PATH_RAY_DTYPE) on a packed INW scene
+    with its lights and textures; the sample tables are sc.params.spp long.  Returns (out
+    (PATH_OUT_DTYPE), stats dict)."""
+    rays = np.ascontiguousarray(rays, PATH_RAY_DTYPE)
+    out = np.zeros(rays.shape, PATH_OUT_DTYPE)
+    st = RtStats()
+    lights = sc.lights if sc.lights is not None and len(sc.lights) else None
+    tex = getattr(sc, "textures", None) or []
+    arr, keep = texture_array(tex)
+    check(load().rt_path_inw(fptr(sc.geom), sc.n, sc.layout, fptr(sc.nodes), fptr(lights), sc.n_lights,
+                             arr if tex else None, len(tex), int(sc.params.spp), int(max_bounces), rays.ctypes.data,
+                             rays.size, int(flags), out.ctypes.data, device, C.byref(st)), "rt_path_inw")
+    del keep
+    return out, st.as_dict()
+
+
+def paths_kernel_info(lights: bool = False, fused: bool = True) -> dict:
+    """rt_debug_paths_kernel: the path-query kernel's registers, scratch, LDS and resident blocks per CU."""
+    info = (C.c_int * 4)()
+    check(load().rt_debug_paths_kernel(int(lights), int(fused), info), "rt_debug_paths_kernel")
     return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
 
 
