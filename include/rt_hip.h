@@ -447,7 +447,8 @@ int rt_trace_iow03(const float *types, const float *records /* N*24 */, uint32_t
  * Returns RT_E_ARG for a null scene, null rays or out with n_rays > 0, a flag bit other than
  * RT_TRACE_INVERT, max_bounces < 0, n_rays > 2^31 or a scene a failed update left broken;
  * RT_E_UNSUPPORTED for an IOW-03 scene: an IOW-03 sample reads the RI stack the previous sample of
- * its pixel left behind, so a single ray has no defined radiance there.  n_rays == 0 returns RT_OK
+ * its pixel left behind, so a single ray has no defined radiance there (rt_path_iow_rays_async,
+ * below, takes that stack state as an input).  n_rays == 0 returns RT_OK
  * and launches nothing.  Every argument error comes back before a device is touched.  Calls on one
  * scene must not overlap each other, its renders or its ray queries (they share its work queue). */
 typedef struct rt_path_ray { float o[3]; uint32_t sample; float d[3]; uint32_t pad; } rt_path_ray;   /* 32 B */
@@ -462,6 +463,62 @@ int rt_path_rays_async(rt_dev_scene *s, const rt_path_ray *d_rays, uint32_t n_ra
 int rt_path_inw(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights, uint32_t n_lights,
                 const rt_texture *tex, int n_tex, int spp, int max_bounces, const rt_path_ray *rays, uint32_t n_rays,
                 int flags, rt_path_out *out, int device, rt_stats *st);
+
+/* ---- path (radiance) queries, IOW-03 ------------------------------------------------------
+ * The same question on an IOW-03 device scene.  One query is one invocation of the reference
+ * shader's LaunchRays (03_Shadows_and_Materials/computeShaderSrc.glsl:285-358) for (o, d): the ray
+ * stack empty and skip = 0, the RI fields of its four slots holding the incoming state ri_in,
+ * push(o, d, contribution = 1, RI = 1, bounced = 0), then the loop to its end.  The RI fields are
+ * all a sample inherits from its pixel's previous one: the stack is empty between samples, skip is
+ * local, and no other slot field is read before it is written.
+ *   - sample picks the scatter table entry fib[sample] of the scene's table; spp is the value the
+ *     scene was created with.  u_NumOfBounce = max_bounces, any value >= 0.  Every segment's limit is
+ *     the shader's 32000; there is no per-ray tmax.  pad is ignored: any bits may be in it.
+ *   - State: ri_in = {0, 0, 0, 0} is what a pixel's first sample sees.  ri_out[e] is slot e's RI
+ *     field when the path ends: the last value the path pushed there, or the incoming value if it
+ *     never wrote the slot.  A pixel's sample s is therefore the query of its camera ray with ri_in
+ *     = the ri_out of sample s - 1, and a frame's pixel is sum(rgb) * RN(1 / spp), as out_Pixel does
+ *     it, bit for bit.
+ *   - stale: bit e is set iff the path used the incoming value of slot e as a parent RI (a hit from
+ *     inside, cos_t > 0, whose parent index pi = size - 1 - skip is in 0..3 and names a slot this
+ *     path has not written yet).  stale == 0: the answer does not depend on ri_in.  More generally,
+ *     changing ri_in[e] for any e whose bit is clear changes nothing but ri_out[e] of an unwritten
+ *     slot.
+ *   - Chains (chain >= 1): queries [k * chain, (k + 1) * chain) form a chain; the last chain may be
+ *     short.  The first query of a chain takes its own ri_in; every later one ignores its ri_in and
+ *     takes its predecessor's outgoing state.  chain = 1: every query is independent.  chain = spp
+ *     with a pixel's camera rays in sample order: one launch answers every sample of that pixel.
+ *   - rgb = the function's return value (`sample`); segments, drops, nans = this path's popped rays,
+ *     pushes dropped by the full 4-entry stack and NaN secondary directions, counted as the renders
+ *     count them; status = 0.
+ *   - sample >= spp: status = 1; rgb, stale and the counts are 0; ri_out is the state on entry (the
+ *     chain passes through it).  No path runs and nothing is counted.
+ *   - Directions are handled by the scene's own search, as in the renders and in
+ *     rt_trace_iow_rays_async: |d|^2 outside (0.998, 1.002) takes the linear loop, a zero or NaN
+ *     direction misses (a NaN direction's rgb is the NaN its background colour is; which NaN is not
+ *     defined); bounce directions are normalised by the shader.
+ *   - The scene's options apply (iow_linear, iow_lds_bvh, iow_leaf_batch); results are bit-identical
+ *     whatever they are.
+ *   - counters: [0] += segments, [4] += dropped pushes, [5] += NaN directions, as the reference
+ *     counts them; [1], [2] this build's own node visits and object tests; [3] untouched.
+ * Returns RT_E_ARG for a null scene (even with n_rays == 0), null rays or out with n_rays > 0,
+ * chain == 0, flags != 0 (reserved), max_bounces < 0 or n_rays > 2^31; RT_E_UNSUPPORTED for an INW
+ * scene; n_rays == 0 returns RT_OK and launches nothing.  Every argument error comes back before a
+ * device is touched, with the output untouched.  Calls on one scene must not overlap each other,
+ * its renders or its ray queries. */
+typedef struct rt_path_iow_ray { float o[3]; uint32_t sample; float d[3]; uint32_t pad; float ri_in[4]; } rt_path_iow_ray;   /* 48 B */
+typedef struct rt_path_iow_out { float rgb[3]; uint32_t stale; uint32_t segments, drops, nans, status; float ri_out[4]; } rt_path_iow_out; /* 48 B */
+/* Device pointers (16-byte aligned); never allocates or synchronises, so it is graph-capturable
+ * like the other queries. */
+int rt_path_iow_rays_async(rt_dev_scene *s, const rt_path_iow_ray *d_rays, uint32_t n_rays, uint32_t chain,
+                           int max_bounces, int flags, rt_path_iow_out *d_out,
+                           uint64_t *d_counters /* 6 x u64, added to; may be NULL */, void *stream);
+/* Blocking: host buffers; builds a device scene for the call like rt_render_iow03 (sample tables of
+ * `spp` entries).  st (may be NULL): the counters and the kernel's device time.  RT_E_ARG also for
+ * null types / records, n == 0 or spp < 1. */
+int rt_path_iow03(const float *types, const float *records /* N*24 */, uint32_t n, int spp, int max_bounces,
+                  const rt_path_iow_ray *rays, uint32_t n_rays, uint32_t chain, int flags,
+                  rt_path_iow_out *out, int device, rt_stats *st);
 
 /* ---- multi-GPU partition (BASELINE configs[3]) -----------------------------
  * One host thread drives several devices of this process: the frame's tiles are dealt

@@ -134,6 +134,11 @@ int rt_debug_paths_kernel(int lights, int fused, int info[4]);
 /* Caps the path-query kernel's grid at `blocks` 256-lane blocks (0 = the default, the resident
  * grid), so that a test can make one block answer many queries.  Returns the previous cap. */
 int rt_debug_paths_max_blocks(int blocks);
+/* The same pair for the IOW-03 path-query kernel (rt_path_iow_rays_async): lds_nodes = 1 the instance
+ * with the BVH staged in LDS, 0 the one that reads nodes from global memory (also the linear
+ * loop's); the cap counts 256-lane blocks, each lane of which owns one chain at a time. */
+int rt_debug_path_iow_kernel(int lds_nodes, int info[4]);
+int rt_debug_path_iow_max_blocks(int blocks);
 
 #ifdef __cplusplus
 }

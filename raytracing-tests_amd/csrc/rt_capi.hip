@@ -78,11 +78,12 @@ int render_temp(const rt_camera *cam, const rt_params *p, float *rgba, float *de
 
 // The blocking ray and path queries: a temporary scene from make(scene), the rays up, trace(scene,
 // rays, hits, counters) timed on the null stream, the hits and the counters back.  Ray / Hit: the
-// 32-byte query and answer records (rt_ray / rt_hit, rt_path_ray / rt_path_out).
+// query and answer records, whole float4s of one size (rt_ray / rt_hit, rt_path_ray / rt_path_out: 32
+// bytes; rt_path_iow_ray / rt_path_iow_out: 48).
 template <class Ray, class Hit, class Make, class Trace>
 int trace_blocking(int flags, int allowed, const Ray *rays, uint32_t n_rays, Hit *hits, int device, rt_stats *st,
                    Make &&make, Trace &&trace) {
-    static_assert(sizeof(Ray) == 32 && sizeof(Hit) == 32, "queries and answers are 2 float4 each");
+    static_assert(sizeof(Ray) == sizeof(Hit) && sizeof(Ray) % 16 == 0, "queries and answers are as many float4 each");
     if ((flags & ~allowed) || n_rays > (1u << 31)) return RT_E_ARG;
     if (n_rays > 0 && (!rays || !hits)) return RT_E_ARG;
     int rc = check_device(device);
@@ -571,6 +572,41 @@ int rt_path_inw(const float *geom, uint32_t n, int layout, const float *nodes, c
         [&](rt_dev_scene *s) { return make_inw(s, geom, n, layout, nodes, lights, n_lights, tex, n_tex, spp); },
         [&](rt_dev_scene *s, const rt_path_ray *d_rays, rt_path_out *d_out, uint64_t *d_ctr) {
             return rt_path_rays_async(s, d_rays, n_rays, max_bounces, flags, d_out, d_ctr, nullptr);
+        });
+}
+
+// ------------------------------------------------------------------------ path queries, IOW-03
+int rt_path_iow_rays_async(rt_dev_scene *s, const rt_path_iow_ray *d_rays, uint32_t n_rays, uint32_t chain,
+                           int max_bounces, int flags, rt_path_iow_out *d_out, uint64_t *d_counters, void *stream) {
+    static_assert(sizeof(rt_path_iow_ray) == 48 && sizeof(rt_path_iow_out) == 48,
+                  "rt_path_iow_ray / rt_path_iow_out are 3 float4 each");
+    if (!s || flags != 0 || chain == 0 || max_bounces < 0) return RT_E_ARG;
+    if (s->kind != 3) return RT_E_UNSUPPORTED;
+    if (n_rays > (1u << 31)) return RT_E_ARG;
+    if (n_rays == 0) return RT_OK;
+    if (!d_rays || !d_out) return RT_E_ARG;
+    const rtk::IowScene sc = iow_view(*s);
+    // its own queue counter: clear of the renders' (word 0; the speculative pipeline's second queue is a
+    // buffer of its own), the INW path queries' (word 224) and the ray queries' (word 240)
+    unsigned *queue = s->counter.as<unsigned>() + 208;
+    const hipError_t e = rtk::launch_iow_paths(sc, s->opt.iow_leaf_batch, max_bounces,
+                                               reinterpret_cast<const float4 *>(d_rays), n_rays, chain, s->spp,
+                                               reinterpret_cast<float4 *>(d_out),
+                                               reinterpret_cast<unsigned long long *>(d_counters), queue, s->cus,
+                                               static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RT_OK : launch_failed(e);
+}
+
+int rt_path_iow03(const float *types, const float *records, uint32_t n, int spp, int max_bounces,
+                  const rt_path_iow_ray *rays, uint32_t n_rays, uint32_t chain, int flags, rt_path_iow_out *out,
+                  int device, rt_stats *st) {
+    if (!types || !records || n == 0 || spp < 1 || max_bounces < 0 || chain == 0) return RT_E_ARG;
+    return trace_blocking(
+        flags, 0, rays, n_rays, out, device, st,
+        // the scene of rt_render_iow03: the scatter table is spp long
+        [&](rt_dev_scene *s) { return make_iow03(s, types, records, n, spp); },
+        [&](rt_dev_scene *s, const rt_path_iow_ray *d_rays, rt_path_iow_out *d_out, uint64_t *d_ctr) {
+            return rt_path_iow_rays_async(s, d_rays, n_rays, chain, max_bounces, flags, d_out, d_ctr, nullptr);
         });
 }
 

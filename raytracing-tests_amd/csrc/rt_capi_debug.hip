@@ -301,4 +301,12 @@ int rt_debug_paths_kernel(int lights, int fused, int info[4]) {
 
 int rt_debug_paths_max_blocks(int blocks) { return rtk::inw_paths_max_blocks(blocks); }
 
+int rt_debug_path_iow_kernel(int lds_nodes, int info[4]) {
+    if (!info) return RT_E_ARG;
+    HIP_OK(rtk::iow_paths_kernel_info(lds_nodes != 0, info));
+    return RT_OK;
+}
+
+int rt_debug_path_iow_max_blocks(int blocks) { return rtk::iow_paths_max_blocks(blocks); }
+
 }  // extern "C"

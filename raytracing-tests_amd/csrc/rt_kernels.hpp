@@ -429,6 +429,18 @@ int inw_paths_blocks_per_cu(bool lights, bool fused);
 // k_inw_paths' {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} (hipFuncGetAttributes)
 hipError_t inw_paths_kernel_info(bool lights, bool fused, int info[4]);
 int inw_paths_max_blocks(int blocks);  // rt_debug_paths_max_blocks: cap the grid (0 = off); the previous cap
+// rt_path_iow.hip: n_rays path queries on an IOW-03 scene (rt_path_iow_ray / rt_path_iow_out as 3 float4
+// each) in chains of `chain` (>= 1) consecutive queries, one chain per persistent lane of a grid of at
+// most cus * iow_paths_blocks_per_cu blocks; queue: one u32 (zeroed here); counters: 6 x u64 added to
+// (slots 0, 1, 2, 4, 5), or null.  iow_lds(sc) picks the LDS-staged instance; sc.nodes == null runs
+// the linear loop; spp: the length of sc.fib / 4; leaf_batch = rt_options.iow_leaf_batch.
+hipError_t launch_iow_paths(const IowScene &sc, int leaf_batch, int max_bounces, const float4 *rays, uint32_t n_rays,
+                            uint32_t chain, int spp, float4 *out, unsigned long long *counters, unsigned *queue,
+                            int cus, hipStream_t s);
+int iow_paths_blocks_per_cu(bool ln);
+// k_iow_paths' {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} (hipFuncGetAttributes)
+hipError_t iow_paths_kernel_info(bool ln, int info[4]);
+int iow_paths_max_blocks(int blocks);  // rt_debug_path_iow_max_blocks: cap the grid (0 = off); the previous cap
 // resident blocks per CU of the render kernel for `kind` (3 = IOW-03 wide, 4 = IOW-03 narrow,
 // 11/14 = INW layout 1/4)
 int resident_blocks_per_cu(int kind);  // 5 = sample-parallel IOW-03, 6/7 = sample-parallel INW 1/4,

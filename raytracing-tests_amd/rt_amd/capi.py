@@ -207,6 +207,12 @@ SIGNATURES = {
                               C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.POINTER(RtStats)]),
     "rt_debug_paths_kernel": (C.c_int, [C.c_int, C.c_int, _IP]),
     "rt_debug_paths_max_blocks": (C.c_int, [C.c_int]),
+    "rt_path_iow_rays_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "rt_path_iow03": (C.c_int, [_FP, _FP, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int,
+                                C.c_void_p, C.c_int, C.POINTER(RtStats)]),
+    "rt_debug_path_iow_kernel": (C.c_int, [C.c_int, _IP]),
+    "rt_debug_path_iow_max_blocks": (C.c_int, [C.c_int]),
     "rt_render_multi_async": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
@@ -593,6 +599,35 @@ def paths_kernel_info(lights: bool = False, fused: bool = True) -> dict:
     """rt_debug_paths_kernel: the path-query kernel's registers, scratch, LDS and resident blocks per CU."""
     info = (C.c_int * 4)()
     check(load().rt_debug_paths_kernel(int(lights), int(fused), info), "rt_debug_paths_kernel")
+    return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
+
+
+# rt_path_iow_ray / rt_path_iow_out (include/rt_hip.h), 48 bytes each
+PATH_IOW_RAY_DTYPE = np.dtype([("o", np.float32, 3), ("sample", np.uint32), ("d", np.float32, 3), ("pad", np.uint32),
+                               ("ri_in", np.float32, 4)])
+PATH_IOW_OUT_DTYPE = np.dtype([("rgb", np.float32, 3), ("stale", np.uint32), ("segments", np.uint32),
+                               ("drops", np.uint32), ("nans", np.uint32), ("status", np.uint32),
+                               ("ri_out", np.float32, 4)])
+
+
+def path_iow(sc: Scene, rays: np.ndarray, max_bounces: int, chain: int = 1, spp: int | None = None,
+             device: int = -1):
+    """rt_path_iow03: blocking path (radiance) queries of `rays` (PATH_IOW_RAY_DTYPE) on a packed IOW-03
+    scene, in chains of `chain`; the scatter table is spp (default sc.params.spp) long.  Returns (out
+    (PATH_IOW_OUT_DTYPE), stats dict)."""
+    rays = np.ascontiguousarray(rays, PATH_IOW_RAY_DTYPE)
+    out = np.zeros(rays.shape, PATH_IOW_OUT_DTYPE)
+    st = RtStats()
+    check(load().rt_path_iow03(fptr(sc.types), fptr(sc.records), sc.n, int(sc.params.spp if spp is None else spp),
+                               int(max_bounces), rays.ctypes.data, rays.size, int(chain), 0, out.ctypes.data, device,
+                               C.byref(st)), "rt_path_iow03")
+    return out, st.as_dict()
+
+
+def path_iow_kernel_info(lds: bool = True) -> dict:
+    """rt_debug_path_iow_kernel: the IOW-03 path-query kernel's registers, scratch, LDS and resident blocks per CU."""
+    info = (C.c_int * 4)()
+    check(load().rt_debug_path_iow_kernel(int(lds), info), "rt_debug_path_iow_kernel")
     return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
 
 
