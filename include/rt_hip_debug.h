@@ -121,6 +121,36 @@ int rt_debug_time_bins(const float *nodes, const float *geom, uint32_t n, uint32
                        uint32_t wnodes_cap, uint32_t info[4]);
 int rt_debug_bin_boxes(const float *geom, uint32_t n, uint32_t bins, uint32_t b, float *boxes_out);
 int rt_debug_sphere_records(const float *geom, uint32_t n, int layout, float *out);
+/* Read-back hooks for the culling and bookkeeping structures (tests/test_walk_structs.py,
+ * tests/test_gpu_walk_structs.py check each one directly against DESIGN.md §2's "every structure is
+ * conservative").  None of them changes what a render path builds or reads.
+ *
+ * rt_debug_walk_dump synchronises and copies one structure of an INW device scene out exactly as the
+ * kernels read it.  info[0] = its size in bytes, info[1..] as listed; with out == NULL only info is
+ * written, otherwise cap_bytes must hold the structure (RT_E_ARG if not).  A structure the scene does
+ * not have (no wide walk, RI grid dropped) has size 0. */
+#define RT_WALK_WNODES   0  /* 10 float4 per node; info = {bytes, nodes, n_wtree0, wbins, wbin_stride, depth} */
+#define RT_WALK_CNODES   1  /* 7 float4 per node; info = {bytes, nodes} */
+#define RT_WALK_QNODES   2  /* info[2] float4 per node; info = {bytes, nodes, float4 per node} */
+#define RT_WALK_LEAFBOX  3  /* 2 float4 per object (its LBVH leaf node); info = {bytes, objects} */
+#define RT_WALK_LBVH     4  /* 2 float4 per LBVH node; info = {bytes, 2 * objects - 1} */
+#define RT_WALK_RI_CELLS 5  /* uint32 cell offsets (cells + 1); info = {bytes, cells, RI grid built} */
+#define RT_WALK_RI_IDS   6  /* uint32 object ids; info = {bytes, ids} */
+#define RT_WALK_RI_FRAME 7  /* float lo[3], hi[3], inv[3], int32 dim[3] as the kernels get them; info = {bytes} */
+#define RT_WALK_WBOUND   8  /* one float; info = {bytes} (ranks and dfs_high: rt_debug_wide_info) */
+int rt_debug_walk_dump(rt_dev_scene *s, int what, void *out, size_t cap_bytes, uint64_t info[8]);
+/* The host builders' full output, no device: rtamd::inw_wide_build and ri_grid_build over the
+ * reference's LBVH nodes ((2n-1) x 8).  info = {wide nodes, dfs_high, wide depth, RI grid built, RI
+ * cells, RI ids, wbound as float bits, 0} (zeros when the LBVH is not walkable).  Every array may be
+ * NULL; one that is not must hold what info reports (wnodes: 40 floats per node; leafbox: 8n; rank:
+ * 2n; ri_cells: cells + 1; ri_ids; ri_frame: lo[3] hi[3] inv[3]; ri_dim[3]). */
+int rt_debug_inw_host_dump(const float *nodes, uint32_t n, uint32_t info[8], float *wnodes, float *leafbox,
+                           uint32_t *rank, uint32_t *ri_cells, uint32_t *ri_ids, float ri_frame[9], int32_t ri_dim[3]);
+/* The same for rtamd::iow_cull_build: info = {wide nodes (0: linear loop), 0, 0, 0}; wide: 32 floats
+ * per node (6 float4 of SoA child planes, the links as int bits, one unused float4); obox: 6n floats as
+ * the kernels read them ((lo xyz, hi x) per object, then (hi y, hi z) per object). */
+int rt_debug_iow_host_dump(const float *types, const float *records, uint32_t n, uint32_t info[4], float *wide,
+                           float *obox);
 /* The ray-query kernel (rt_trace_rays_async) as the loaded code object has it: info = {VGPRs,
  * scratch bytes per lane, static LDS bytes per block, resident 256-lane blocks per CU} of the
  * closest-hit (any = 0) or RT_TRACE_ANY instance, with the fused cull or without.  Needs a device. */

@@ -281,6 +281,101 @@ int rt_debug_sphere_records(const float *geom, uint32_t n, int layout, float *ou
     return 1;
 }
 
+int rt_debug_walk_dump(rt_dev_scene *s, int what, void *out, size_t cap_bytes, uint64_t info[8]) {
+    if (!s || s->kind == 3 || s->broken || !info) return RT_E_ARG;
+    HIP_OK(hipSetDevice(s->device));
+    HIP_OK(hipDeviceSynchronize());
+    const InwWalk &w = s->walk;
+    uint64_t v[8] = {};
+    const DevBuf *src = nullptr;
+    const void *host = nullptr;  // RI frame and wbound live in the scene, not in a device buffer
+    struct { float f[9]; int32_t dim[3]; } frame{};
+    const size_t nw = w.n_wnodes, n = s->n;
+    const size_t cells = w.ri_ok ? size_t(w.ri_dim[0]) * size_t(w.ri_dim[1]) * size_t(w.ri_dim[2]) : 0;
+    switch (what) {
+    case RT_WALK_WNODES:
+        src = &w.wnodes; v[0] = nw * 10 * sizeof(float4); v[1] = nw; v[2] = w.n_wtree0; v[3] = w.wbins;
+        v[4] = w.wbin_stride; v[5] = uint64_t(w.wdepth);
+        break;
+    case RT_WALK_CNODES: src = &w.cnodes; v[0] = nw * 7 * sizeof(float4); v[1] = nw; break;
+    case RT_WALK_QNODES: src = &w.qnodes; v[0] = nw * rtk::kQNodeF4 * sizeof(float4); v[1] = nw; v[2] = rtk::kQNodeF4; break;
+    case RT_WALK_LEAFBOX: src = &w.wleaf; v[0] = nw ? n * 2 * sizeof(float4) : 0; v[1] = nw ? n : 0; break;
+    case RT_WALK_LBVH: src = &s->nodes; v[0] = n ? (2 * n - 1) * 2 * sizeof(float4) : 0; v[1] = n ? 2 * n - 1 : 0; break;
+    case RT_WALK_RI_CELLS: src = &w.ri_cells; v[0] = cells ? (cells + 1) * sizeof(uint32_t) : 0; v[1] = cells; v[2] = w.ri_ok; break;
+    case RT_WALK_RI_IDS: {
+        src = &w.ri_ids;
+        uint32_t total = 0;
+        if (cells) {
+            if (w.ri_cells.bytes < (cells + 1) * sizeof(uint32_t)) return RT_E_ARG;
+            HIP_OK(hipMemcpy(&total, w.ri_cells.as<uint32_t>() + cells, sizeof(total), hipMemcpyDeviceToHost));
+        }
+        v[0] = size_t(total) * sizeof(uint32_t); v[1] = total;
+        break;
+    }
+    case RT_WALK_RI_FRAME:
+        for (int a = 0; a < 3; a++) {
+            frame.f[a] = w.ri_lo[a]; frame.f[3 + a] = w.ri_hi[a]; frame.f[6 + a] = w.ri_inv[a]; frame.dim[a] = w.ri_dim[a];
+        }
+        host = &frame; v[0] = w.ri_ok ? sizeof(frame) : 0;
+        break;
+    case RT_WALK_WBOUND: host = &w.wbound; v[0] = nw ? sizeof(float) : 0; break;
+    default: return RT_E_ARG;
+    }
+    std::memcpy(info, v, sizeof(v));
+    if (!out || !v[0]) return RT_OK;
+    if (cap_bytes < v[0]) return RT_E_ARG;
+    if (host) { std::memcpy(out, host, size_t(v[0])); return RT_OK; }
+    if (!src->p || src->bytes < v[0]) return RT_E_ARG;  // never read past the allocation
+    HIP_OK(hipMemcpy(out, src->p, size_t(v[0]), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_debug_inw_host_dump(const float *nodes, uint32_t n, uint32_t info[8], float *wnodes, float *leafbox,
+                           uint32_t *rank, uint32_t *ri_cells, uint32_t *ri_ids, float ri_frame[9], int32_t ri_dim[3]) {
+    if (!nodes || n == 0 || !info) return RT_E_ARG;
+    try {
+        std::memset(info, 0, 8 * sizeof(uint32_t));
+        rtamd::InwWide w;
+        if (!rtamd::inw_wide_build(nodes, n, w)) return RT_OK;
+        const rtamd::RiGrid g = rtamd::ri_grid_build(w.leafbox.data(), n);
+        uint32_t wb = 0;
+        std::memcpy(&wb, &w.wbound, sizeof(wb));
+        const uint32_t v[8] = {uint32_t(w.wnodes.size() / 40), w.dfs_high, uint32_t(w.depth), g.ok ? 1u : 0u,
+                               g.ok ? uint32_t(g.cells.size() - 1) : 0u, uint32_t(g.ids.size()), wb, 0u};
+        std::memcpy(info, v, sizeof(v));
+        if (wnodes) std::memcpy(wnodes, w.wnodes.data(), w.wnodes.size() * sizeof(float));
+        if (leafbox) std::memcpy(leafbox, w.leafbox.data(), w.leafbox.size() * sizeof(float));
+        if (rank) std::memcpy(rank, w.rank.data(), w.rank.size() * sizeof(uint32_t));
+        if (g.ok) {
+            if (ri_cells) std::memcpy(ri_cells, g.cells.data(), g.cells.size() * sizeof(uint32_t));
+            if (ri_ids && !g.ids.empty()) std::memcpy(ri_ids, g.ids.data(), g.ids.size() * sizeof(uint32_t));
+            for (int a = 0; a < 3; a++) {
+                if (ri_frame) { ri_frame[a] = g.lo[a]; ri_frame[3 + a] = g.hi[a]; ri_frame[6 + a] = g.inv[a]; }
+                if (ri_dim) ri_dim[a] = g.dim[a];
+            }
+        }
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_debug_iow_host_dump(const float *types, const float *records, uint32_t n, uint32_t info[4], float *wide,
+                           float *obox) {
+    if (!types || !records || n == 0 || !info) return RT_E_ARG;
+    try {
+        std::memset(info, 0, 4 * sizeof(uint32_t));
+        rtamd::IowCull c;
+        if (!rtamd::iow_cull_build(types, records, n, c)) return RT_OK;
+        info[0] = c.n_wide;
+        if (wide) std::memcpy(wide, c.wide.data(), c.wide.size() * sizeof(float));
+        if (obox) std::memcpy(obox, c.obox.data(), c.obox.size() * sizeof(float));
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    return RT_OK;
+}
+
 int rt_debug_trace_kernel(int any, int fused, int info[4]) {
     if (!info) return RT_E_ARG;
     HIP_OK(rtk::inw_trace_kernel_info(any != 0, fused != 0, info));

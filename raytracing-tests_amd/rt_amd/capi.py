@@ -190,6 +190,9 @@ SIGNATURES = {
     "rt_debug_time_bins": (C.c_int, [_FP, _FP, C.c_uint32, C.c_uint32, _FP, C.c_uint32, _U32P]),
     "rt_debug_bin_boxes": (C.c_int, [_FP, C.c_uint32, C.c_uint32, C.c_uint32, _FP]),
     "rt_debug_sphere_records": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP]),
+    "rt_debug_walk_dump": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, _U64P]),
+    "rt_debug_inw_host_dump": (C.c_int, [_FP, C.c_uint32, _U32P, _FP, _FP, _U32P, _U32P, _U32P, _FP, _IP]),
+    "rt_debug_iow_host_dump": (C.c_int, [_FP, _FP, C.c_uint32, _U32P, _FP, _FP]),
     "rt_group_free": (None, [C.c_void_p]),
     "rt_trace_rays_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
@@ -479,6 +482,100 @@ def iow_host_build(types: np.ndarray, records: np.ndarray, n: int) -> dict:
     ms = C.c_double(0.0)
     check(load().rt_iow_host_build(fptr(types), fptr(records), n, info, C.byref(ms)), "rt_iow_host_build")
     return {"wide_nodes": info[0], "ms": ms.value}
+
+
+def inw_host_dump(nodes: np.ndarray, n: int) -> dict | None:
+    """rt_debug_inw_host_dump: everything inw_wide_build and ri_grid_build make of an LBVH node buffer
+    (None: not walkable).  wnodes (N, 40) float32 with the links as int bits; the ri_* entries are None
+    when the grid was dropped (ri_grid = 0)."""
+    lib = load()
+    nodes = np.ascontiguousarray(nodes, np.float32)
+    info = (C.c_uint32 * 8)()
+    check(lib.rt_debug_inw_host_dump(fptr(nodes), n, info, None, None, None, None, None, None, None),
+          "rt_debug_inw_host_dump")
+    nw, high, depth, ok, cells, nids, wb = list(info)[:7]
+    if not nw:
+        return None
+    wn = np.zeros((nw, 40), np.float32)
+    leaf = np.zeros((n, 8), np.float32)
+    rank = np.zeros((2, n), np.uint32)
+    rc = np.zeros(cells + 1, np.uint32)
+    ri = np.zeros(max(1, nids), np.uint32)
+    frame = np.zeros(9, np.float32)
+    dim = np.zeros(3, np.int32)
+    check(lib.rt_debug_inw_host_dump(fptr(nodes), n, info, fptr(wn), fptr(leaf), rank.ctypes.data_as(_U32P),
+                                     rc.ctypes.data_as(_U32P), ri.ctypes.data_as(_U32P), fptr(frame),
+                                     dim.ctypes.data_as(_IP)), "rt_debug_inw_host_dump")
+    out = {"wnodes": wn, "n_wtree0": nw, "wbins": 1, "wbin_stride": 0, "leafbox": leaf, "rank": rank,
+           "dfs_high": high, "depth": depth, "wbound": np.array([wb], np.uint32).view(np.float32)[0], "ri_grid": ok,
+           "ri_cells": None, "ri_ids": None, "ri_lo": None, "ri_hi": None, "ri_inv": None, "ri_dim": None}
+    if ok:
+        out.update(ri_cells=rc, ri_ids=ri[:nids], ri_lo=frame[0:3], ri_hi=frame[3:6], ri_inv=frame[6:9], ri_dim=dim)
+    return out
+
+
+def iow_host_dump(types: np.ndarray, records: np.ndarray, n: int) -> dict | None:
+    """rt_debug_iow_host_dump: the IOW-03 culling BVH (wide (N, 32) float32, links as int bits in
+    columns 24..27) and the per-object boxes obox (n, 6) (lo xyz, hi xyz), unpacked from the kernels'
+    layout.  None: no BVH (the linear loop)."""
+    lib = load()
+    types = np.ascontiguousarray(types, np.float32)
+    records = np.ascontiguousarray(records, np.float32)
+    info = (C.c_uint32 * 4)()
+    check(lib.rt_debug_iow_host_dump(fptr(types), fptr(records), n, info, None, None), "rt_debug_iow_host_dump")
+    if not info[0]:
+        return None
+    wide = np.zeros((info[0], 32), np.float32)
+    raw = np.zeros(6 * n, np.float32)
+    check(lib.rt_debug_iow_host_dump(fptr(types), fptr(records), n, info, fptr(wide), fptr(raw)),
+          "rt_debug_iow_host_dump")
+    obox = np.concatenate([raw[:4 * n].reshape(n, 4), raw[4 * n:].reshape(n, 2)], axis=1)
+    return {"wide": wide, "obox": obox}
+
+
+RT_WALK_WNODES, RT_WALK_CNODES, RT_WALK_QNODES, RT_WALK_LEAFBOX, RT_WALK_LBVH = 0, 1, 2, 3, 4
+RT_WALK_RI_CELLS, RT_WALK_RI_IDS, RT_WALK_RI_FRAME, RT_WALK_WBOUND = 5, 6, 7, 8
+
+
+def walk_dump(scene, what: int, dtype=np.float32):
+    """rt_debug_walk_dump: one structure of an INW device scene (a handle from rt_dev_scene_inw*) as a
+    flat array of `dtype`, and the hook's info list."""
+    lib = load()
+    info = (C.c_uint64 * 8)()
+    check(lib.rt_debug_walk_dump(scene, what, None, 0, info), "rt_debug_walk_dump")
+    out = np.zeros(int(info[0]) // np.dtype(dtype).itemsize, dtype)
+    if info[0]:
+        check(lib.rt_debug_walk_dump(scene, what, out.ctypes.data, out.nbytes, info), "rt_debug_walk_dump")
+    return out, [int(x) for x in info]
+
+
+def walk_dump_all(scene) -> dict:
+    """Every structure rt_debug_walk_dump and rt_debug_wide_info read back, in inw_host_dump's keys plus
+    cnodes (N, 28), qnodes (N, 4 * float4 per node), lbvh (2n-1, 8), n and build (where it was built)."""
+    lib = load()
+    wi = (C.c_uint32 * 8)()
+    check(lib.rt_debug_wide_info(scene, wi, None), "rt_debug_wide_info")
+    n = int(wi[6])
+    rank = np.zeros((2, n), np.uint32)
+    check(lib.rt_debug_wide_info(scene, wi, rank.ctypes.data_as(_U32P)), "rt_debug_wide_info")
+    wn, iw = walk_dump(scene, RT_WALK_WNODES)
+    cn, _ = walk_dump(scene, RT_WALK_CNODES)
+    qn, iq = walk_dump(scene, RT_WALK_QNODES)
+    leaf, _ = walk_dump(scene, RT_WALK_LEAFBOX)
+    lbvh, _ = walk_dump(scene, RT_WALK_LBVH)
+    cells, ic = walk_dump(scene, RT_WALK_RI_CELLS, np.uint32)
+    ids, _ = walk_dump(scene, RT_WALK_RI_IDS, np.uint32)
+    frame, _ = walk_dump(scene, RT_WALK_RI_FRAME)
+    wb, _ = walk_dump(scene, RT_WALK_WBOUND)
+    ok = int(ic[2])
+    return {"n": n, "build": int(wi[7]), "wnodes": wn.reshape(-1, 40), "n_wtree0": iw[2], "wbins": iw[3],
+            "wbin_stride": iw[4], "depth": iw[5], "cnodes": cn.reshape(-1, 28),
+            "qnodes": qn.reshape(-1, 4 * max(1, iq[2])), "leafbox": leaf.reshape(-1, 8), "lbvh": lbvh.reshape(-1, 8),
+            "rank": rank, "dfs_high": int(wi[1]), "wbound": wb[0] if len(wb) else None, "ri_grid": ok,
+            "ri_cells": cells if ok else None, "ri_ids": ids if ok else None,
+            "ri_lo": frame[0:3] if ok else None, "ri_hi": frame[3:6] if ok else None,
+            "ri_inv": frame[6:9] if ok else None, "ri_dim": frame[9:12].view(np.int32) if ok else None,
+            "wide_info": [int(x) for x in wi]}
 
 
 def lbvh_build(aabbs: np.ndarray) -> np.ndarray:
