@@ -520,6 +520,80 @@ int rt_path_iow03(const float *types, const float *records /* N*24 */, uint32_t 
                   const rt_path_iow_ray *rays, uint32_t n_rays, uint32_t chain, int flags,
                   rt_path_iow_out *out, int device, rt_stats *st);
 
+/* ---- pixel queries --------------------------------------------------------------------------
+ * The two ends of the path queries' theorem as entry points: the shader's own camera ray of (pixel,
+ * sample), and the shader's fold of a pixel's answers.  With them "what is pixel (x, y) of this
+ * frame, and what did each of its samples contribute?" is one call: no W x H render, no host
+ * arithmetic, nothing of out_Pixel's prologue to restate.
+ *
+ * rt_camera_rays_async writes the camera rays of samples [s0, s0 + ns) of n_pixels pixels as
+ * path-query records: rt_path_ray (32 B) on an INW scene, rt_path_iow_ray (48 B, ri_in = 0) on an
+ * IOW-03 one.  Record k * ns + j is the ray of pixel d_pixels[k], sample s0 + j, with sample = s0 + j
+ * and pad = 0: pixel-major, so an IOW-03 pixel is one chain of ns consecutive records.
+ *   - The rays are, bit for bit, what the render kernels push for that pixel and sample -- the
+ *     kernel calls the renders' own device functions.  INW: out_Pixel's prologue
+ *     (01_BoundingVolumeHierarchy/computeShaderSrc.glsl:366-410), the single-focus branch: origin
+ *     tip - la, direction la.  IOW-03: 03_Shadows_and_Materials/computeShaderSrc.glsl:370-406 with
+ *     the scene's sunflower and ring tables.
+ *   - y is pixel_coords.y: the GL image's bottom row first, the row index of the renders' output.
+ *   - p->width, p->height and p->spp are read; p->spp must equal the scene's, as for the renders.
+ *     p->tile_*, p->max_bounces and p->show_normal are ignored.  The frame uniforms (screen_dist,
+ *     1 / spp) are formed as the renders form them.
+ *   - A pixel outside [0, W) x [0, H) and a sample index >= spp (s0 + ns may overrun) get sample =
+ *     0xffffffff and every other field 0, which the path queries answer with status = 1.  So does an
+ *     IOW-03 sample whose ring entry is the shader's early-return marker (03...glsl:396); with the
+ *     tables rt_sample_tables builds no spp >= 1 has one.
+ * Returns RT_E_ARG for a null scene, cam or p, bad params (width, height, spp < 1, max_bounces < 0),
+ * p->spp != the scene's, null d_pixels or d_rays with n_pixels * ns > 0, n_pixels * ns > 2^31 or a
+ * scene a failed update left broken; n_pixels == 0 or ns == 0 returns RT_OK and launches nothing.
+ * Every argument error comes back before a device is touched. */
+typedef struct rt_pixel { int32_t x, y; } rt_pixel;   /* 8 B; y = pixel_coords.y, GL bottom row first */
+/* Device pointers (d_rays 16-byte aligned); never allocates or synchronises. */
+int rt_camera_rays_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p,
+                         const rt_pixel *d_pixels, uint32_t n_pixels, uint32_t s0, uint32_t ns,
+                         void *d_rays, void *stream);
+/* rt_pixel_query_async answers n_pixels pixels of the frame (cam, p).  It enqueues, with nothing else
+ * in between: the camera rays of all spp samples into the workspace; the unchanged path kernel on
+ * them (INW: max_bounces = p->max_bounces and RT_TRACE_INVERT exactly when dot(cam->dir, (1, 1, 1))
+ * > 0 in binary32 in the shader's order; IOW-03: chain = spp); the fold, one rt_pixel_out per pixel:
+ *   - INW: rgb = End()'s fold (01_BVH...glsl:625-675): the first sample's sqrt(colour) assigned, the
+ *     others added in sample order, times RN(1 / spp); alpha = 1; depth = the depth of sample
+ *     spp / 2.
+ *   - IOW-03: rgb = the samples' rgb added in order from 0, times RN(1 / spp) (a pixel stops at its
+ *     first status = 1 answer, sample s, and is scaled by RN(1 / s): the shader's early return);
+ *     alpha = 1; depth = 0.
+ *   - segments, drops, nans = the sums over the pixel's samples.
+ *   - A pixel outside the image gives an all-zero record.
+ * rgba and depth are, bit for bit, what rt_render_image_async writes at that pixel for the same cam
+ * and p; counters [0], [3], [4], [5], added over all pixels of a frame, are the render's.
+ * The per-sample answers (n_pixels * spp rt_path_out / rt_path_iow_out, pixel-major) go to
+ * d_samples_out when given, else into the workspace.  d_ws: rt_pixel_workspace_bytes(s, n_pixels)
+ * bytes (the rays plus the samples: one size serves both cases; 0 for a null scene).  After the call
+ * the workspace's first n_pixels * spp records are the camera rays.
+ * Returns RT_E_ARG as rt_camera_rays_async does (with ns = spp), for a null d_pixels_out or d_ws with
+ * n_pixels > 0 and for ws_bytes too small; then RT_E_UNSUPPORTED for p->show_normal != 0 (that mode
+ * is not a path).  n_pixels == 0 returns RT_OK and launches nothing.  Calls on one scene must not
+ * overlap each other, its renders or its queries. */
+typedef struct rt_pixel_out { float rgba[4]; float depth; uint32_t segments, drops, nans; } rt_pixel_out;  /* 32 B */
+size_t rt_pixel_workspace_bytes(const rt_dev_scene *s, uint32_t n_pixels);
+/* Device pointers (16-byte aligned); never allocates or synchronises, so it is graph-capturable. */
+int rt_pixel_query_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p,
+                         const rt_pixel *d_pixels, uint32_t n_pixels,
+                         rt_pixel_out *d_pixels_out,
+                         void *d_samples_out /* n_pixels * spp rt_path_out / rt_path_iow_out, may be NULL */,
+                         void *d_ws, size_t ws_bytes,
+                         uint64_t *d_counters /* 6 x u64, added to; may be NULL */, void *stream);
+/* Blocking: host buffers; build a device scene for the call like rt_path_inw / rt_path_iow03 (sample
+ * tables of p->spp entries).  rays_out and samples_out (n_pixels * p->spp records each) may be NULL.
+ * st (may be NULL): the counters and the three kernels' device time. */
+int rt_pixels_inw(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                  uint32_t n_lights, const rt_texture *tex, int n_tex, const rt_camera *cam, const rt_params *p,
+                  const rt_pixel *pixels, uint32_t n_pixels, rt_path_ray *rays_out, rt_path_out *samples_out,
+                  rt_pixel_out *pixels_out, int device, rt_stats *st);
+int rt_pixels_iow03(const float *types, const float *records /* N*24 */, uint32_t n, const rt_camera *cam,
+                    const rt_params *p, const rt_pixel *pixels, uint32_t n_pixels, rt_path_iow_ray *rays_out,
+                    rt_path_iow_out *samples_out, rt_pixel_out *pixels_out, int device, rt_stats *st);
+
 /* ---- multi-GPU partition (BASELINE configs[3]) -----------------------------
  * One host thread drives several devices of this process: the frame's tiles are dealt
  * across the devices, each renders its share with rt_render_tiles_async on a stream of its own,

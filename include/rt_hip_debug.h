@@ -169,6 +169,10 @@ int rt_debug_paths_max_blocks(int blocks);
  * loop's); the cap counts 256-lane blocks, each lane of which owns one chain at a time. */
 int rt_debug_path_iow_kernel(int lds_nodes, int info[4]);
 int rt_debug_path_iow_max_blocks(int blocks);
+/* The same for the pixel-query kernels (rt_camera_rays_async, rt_pixel_query_async): which = 0
+ * k_camera_rays on an INW scene, 1 on an IOW-03 scene, 2 k_pixel_fold INW, 3 IOW-03 (blocks of 256
+ * lanes: 256 records of rays, four pixels of the fold).  RT_E_ARG for any other `which`. */
+int rt_debug_pixels_kernel(int which, int info[4]);
 
 #ifdef __cplusplus
 }

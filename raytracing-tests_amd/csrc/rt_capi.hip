@@ -113,6 +113,55 @@ int trace_blocking(int flags, int allowed, const Ray *rays, uint32_t n_rays, Hit
     return st ? read_stats(d_ctr.p, ms, st) : RT_OK;
 }
 
+// Pixel queries: the bytes of one path query / answer record of the scene's family, and the
+// workspace of n_pixels pixels: their spp rays plus their spp answers.
+size_t pixel_record_bytes(const rt_dev_scene *s) { return s->kind == 3 ? sizeof(rt_path_iow_ray) : sizeof(rt_path_ray); }
+size_t pixel_ws_bytes(const rt_dev_scene *s, uint32_t n_pixels) {
+    return size_t(n_pixels) * size_t(s->spp) * pixel_record_bytes(s) * 2;
+}
+bool pixels_args_ok(const rt_params *p, const rt_pixel *pixels, uint32_t n_pixels, const rt_pixel_out *pixels_out) {
+    return uint64_t(n_pixels) * uint32_t(p->spp) <= (uint64_t(1) << 31) && (n_pixels == 0 || (pixels && pixels_out));
+}
+
+// The blocking pixel queries: a temporary scene from make(scene), the pixels up, rt_pixel_query_async
+// timed on the null stream, the pixels (and, when asked for, the rays and the samples, both left in
+// the workspace) and the counters back.
+template <class Ray, class Out, class Make>
+int pixels_blocking(const rt_camera *cam, const rt_params *p, const rt_pixel *pixels, uint32_t n_pixels, Ray *rays_out,
+                    Out *samples_out, rt_pixel_out *pixels_out, int device, rt_stats *st, Make &&make) {
+    static_assert(sizeof(Ray) == sizeof(Out), "queries and answers are as many float4 each");
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    std::unique_ptr<rt_dev_scene> s = temp_scene();
+    if (!s) return RT_E_ARG;
+    try {  // the host builders allocate: no exception crosses the ABI
+        rc = make(s.get());
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    if (rc != RT_OK) return rc;
+    if (st) std::memset(st, 0, sizeof(*st));
+    if (n_pixels == 0) return RT_OK;
+    DevBuf d_px, d_out, d_ws, d_ctr;
+    const size_t rec_bytes = size_t(n_pixels) * size_t(p->spp) * sizeof(Ray);
+    HIP_OK(d_px.upload(pixels, size_t(n_pixels) * sizeof(rt_pixel)));
+    HIP_OK(d_out.alloc(size_t(n_pixels) * sizeof(rt_pixel_out)));
+    HIP_OK(d_ws.alloc(pixel_ws_bytes(s.get(), n_pixels)));
+    HIP_OK(d_ctr.alloc(6 * sizeof(unsigned long long)));
+    HIP_OK(hipMemset(d_ctr.p, 0, 6 * sizeof(unsigned long long)));
+    double ms = 0.0;
+    rc = timed([&] {
+        return rt_pixel_query_async(s.get(), cam, p, d_px.as<rt_pixel>(), n_pixels, d_out.as<rt_pixel_out>(), nullptr,
+                                    d_ws.p, d_ws.bytes, d_ctr.as<uint64_t>(), nullptr);
+    }, &ms);
+    if (rc != RT_OK) return rc;
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(pixels_out, d_out.p, size_t(n_pixels) * sizeof(rt_pixel_out), hipMemcpyDeviceToHost));
+    if (rays_out) HIP_OK(hipMemcpy(rays_out, d_ws.p, rec_bytes, hipMemcpyDeviceToHost));
+    if (samples_out) HIP_OK(hipMemcpy(samples_out, d_ws.as<char>() + rec_bytes, rec_bytes, hipMemcpyDeviceToHost));
+    return st ? read_stats(d_ctr.p, ms, st) : RT_OK;
+}
+
 }  // namespace
 
 rt_options g_opt = default_options();
@@ -608,6 +657,86 @@ int rt_path_iow03(const float *types, const float *records, uint32_t n, int spp,
         [&](rt_dev_scene *s, const rt_path_iow_ray *d_rays, rt_path_iow_out *d_out, uint64_t *d_ctr) {
             return rt_path_iow_rays_async(s, d_rays, n_rays, chain, max_bounces, flags, d_out, d_ctr, nullptr);
         });
+}
+
+// ------------------------------------------------------------------------ pixel queries
+int rt_camera_rays_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p, const rt_pixel *d_pixels,
+                         uint32_t n_pixels, uint32_t s0, uint32_t ns, void *d_rays, void *stream) {
+    static_assert(sizeof(rt_pixel) == 8 && sizeof(rt_pixel) == sizeof(int2), "rt_pixel is an (x, y) int pair");
+    if (!s || !cam || !params_ok(p) || p->spp != s->spp || s->broken) return RT_E_ARG;
+    const uint64_t n = uint64_t(n_pixels) * ns;
+    if (n > (uint64_t(1) << 31)) return RT_E_ARG;
+    if (n == 0) return RT_OK;
+    if (!d_pixels || !d_rays) return RT_E_ARG;
+    const rtk::Frame f = make_frame(cam, p);
+    const int2 *px = reinterpret_cast<const int2 *>(d_pixels);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const hipError_t e = s->kind == 3 ? rtk::launch_camera_rays(f, iow_view(*s), px, uint32_t(n), s0, ns,
+                                                                static_cast<float4 *>(d_rays), st)
+                                      : rtk::launch_camera_rays(f, inw_view(*s), px, uint32_t(n), s0, ns,
+                                                                static_cast<float4 *>(d_rays), st);
+    return e == hipSuccess ? RT_OK : launch_failed(e);
+}
+
+size_t rt_pixel_workspace_bytes(const rt_dev_scene *s, uint32_t n_pixels) {
+    return s ? pixel_ws_bytes(s, n_pixels) : 0;
+}
+
+int rt_pixel_query_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p, const rt_pixel *d_pixels,
+                         uint32_t n_pixels, rt_pixel_out *d_pixels_out, void *d_samples_out, void *d_ws,
+                         size_t ws_bytes, uint64_t *d_counters, void *stream) {
+    static_assert(sizeof(rt_pixel_out) == 32, "rt_pixel_out is 2 float4");
+    if (!s || !cam || !params_ok(p) || p->spp != s->spp || s->broken) return RT_E_ARG;
+    const uint64_t n = uint64_t(n_pixels) * uint32_t(p->spp);
+    if (n > (uint64_t(1) << 31)) return RT_E_ARG;
+    if (n_pixels > 0 && (!d_pixels || !d_pixels_out || !d_ws || ws_bytes < pixel_ws_bytes(s, n_pixels))) return RT_E_ARG;
+    if (p->show_normal) return RT_E_UNSUPPORTED;  // one normal per sample, no path
+    if (n_pixels == 0) return RT_OK;
+    const bool iow = s->kind == 3;
+    void *samples = d_samples_out ? d_samples_out : static_cast<char *>(d_ws) + size_t(n) * pixel_record_bytes(s);
+    int rc = rt_camera_rays_async(s, cam, p, d_pixels, n_pixels, 0, uint32_t(p->spp), d_ws, stream);
+    if (rc != RT_OK) return rc;
+    if (iow) {
+        rc = rt_path_iow_rays_async(s, static_cast<const rt_path_iow_ray *>(d_ws), uint32_t(n), uint32_t(p->spp),
+                                    p->max_bounces, 0, static_cast<rt_path_iow_out *>(samples), d_counters, stream);
+    } else {
+        // the frame's child order: dot(dir, (1, 1, 1)) > 0 in binary32, the shader's order (inw_segment)
+        const float dsum = (cam->dir[0] * 1.0f + cam->dir[1] * 1.0f) + cam->dir[2] * 1.0f;
+        rc = rt_path_rays_async(s, static_cast<const rt_path_ray *>(d_ws), uint32_t(n), p->max_bounces,
+                                dsum > 0.0f ? RT_TRACE_INVERT : 0, static_cast<rt_path_out *>(samples), d_counters,
+                                stream);
+    }
+    if (rc != RT_OK) return rc;
+    const hipError_t e = rtk::launch_pixel_fold(make_frame(cam, p), iow, reinterpret_cast<const int2 *>(d_pixels),
+                                                n_pixels, static_cast<const float4 *>(samples),
+                                                reinterpret_cast<float4 *>(d_pixels_out),
+                                                static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RT_OK : launch_failed(e);
+}
+
+int rt_pixels_inw(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                  uint32_t n_lights, const rt_texture *tex, int n_tex, const rt_camera *cam, const rt_params *p,
+                  const rt_pixel *pixels, uint32_t n_pixels, rt_path_ray *rays_out, rt_path_out *samples_out,
+                  rt_pixel_out *pixels_out, int device, rt_stats *st) {
+    if (!geom || !nodes || n == 0 || (layout != 1 && layout != 4) || !cam || !params_ok(p)) return RT_E_ARG;
+    if (layout == 4 && n_lights > 0 && !lights) return RT_E_ARG;
+    if (!textures_ok(tex, n_tex)) return RT_E_ARG;
+    if (!pixels_args_ok(p, pixels, n_pixels, pixels_out)) return RT_E_ARG;
+    if (n_tex == 0 && inw_textured(geom, n, layout)) return RT_E_UNSUPPORTED;  // no texture bound
+    if (p->show_normal) return RT_E_UNSUPPORTED;
+    return pixels_blocking(cam, p, pixels, n_pixels, rays_out, samples_out, pixels_out, device, st, [&](rt_dev_scene *s) {
+        return make_inw(s, geom, n, layout, nodes, lights, n_lights, tex, n_tex, p->spp);
+    });
+}
+
+int rt_pixels_iow03(const float *types, const float *records, uint32_t n, const rt_camera *cam, const rt_params *p,
+                    const rt_pixel *pixels, uint32_t n_pixels, rt_path_iow_ray *rays_out, rt_path_iow_out *samples_out,
+                    rt_pixel_out *pixels_out, int device, rt_stats *st) {
+    if (!types || !records || n == 0 || !cam || !params_ok(p)) return RT_E_ARG;
+    if (!pixels_args_ok(p, pixels, n_pixels, pixels_out)) return RT_E_ARG;
+    if (p->show_normal) return RT_E_UNSUPPORTED;
+    return pixels_blocking(cam, p, pixels, n_pixels, rays_out, samples_out, pixels_out, device, st,
+                           [&](rt_dev_scene *s) { return make_iow03(s, types, records, n, p->spp); });
 }
 
 // ------------------------------------------------------------------------ rt_scene.h

@@ -404,4 +404,10 @@ int rt_debug_path_iow_kernel(int lds_nodes, int info[4]) {
 
 int rt_debug_path_iow_max_blocks(int blocks) { return rtk::iow_paths_max_blocks(blocks); }
 
+int rt_debug_pixels_kernel(int which, int info[4]) {
+    if (!info || which < 0 || which > 3) return RT_E_ARG;
+    HIP_OK(rtk::pixels_kernel_info(which, info));
+    return RT_OK;
+}
+
 }  // extern "C"

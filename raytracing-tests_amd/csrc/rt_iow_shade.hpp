@@ -136,4 +136,38 @@ __device__ __forceinline__ void iow_segment(const IowScene &S, const Frame &F, I
     iow_seg_shade(S, F, K, skip, sample, sidx, c, in, data);
 }
 
+// Camera ray of sample s of a pixel, out_Pixel 03...glsl:370-406
+struct IowPixelCam { float sx, sy; };
+__device__ __forceinline__ void iow_camera_ray(const IowScene &S, const Frame &f, float sx, float sy, float dsx,
+                                               float dsy, int s, f3 &ro, f3 &rd) {
+    const f3 D = mk(f.dir[0], f.dir[1], f.dir[2]), P = mk(f.pos[0], f.pos[1], f.pos[2]);
+    const f3 up = f3{0, 1, 0};
+    f3 look_at = P + D * f.focus;
+    f3 cr = cross(D, up), cu = cross(cr, D);
+    const int ix = S.ring[2 * s], iy = S.ring[2 * s + 1];
+    float rx = (S.sunflower[2 * s] * f.aperture) * 0.5f, ry = (S.sunflower[2 * s + 1] * f.aperture) * 0.5f;
+    ro = (P + cr * rx) + cu * ry;
+    f3 ld = normalize(look_at - ro);
+    f3 r_ = cross(ld, up), u_ = cross(cr, ld);
+    rd = normalize((ld * f.screen_dist + r_ * (sx + dsx * (float)ix)) + u_ * (sy + dsy * (float)iy));
+}
+// The four scalars it takes, as out_Pixel forms them (03...glsl:370-380): the pixel's screen position
+// (sx, sy) and the sub-pixel steps (dsx, dsy).  The render kernels (rt_kernels.hip) and k_camera_rays
+// (rt_pixels.hip) call these.
+// The ring schedule's grid and the aspect ratio under them: k_camera_rays calls these two; the render
+// kernels keep the same two statements inline (calling them here changed their device code's bytes,
+// the grid loop's).
+__device__ __forceinline__ int iow_ring_grid(int spp) {
+    int grid = 1;
+    while (grid * grid < spp) grid++;
+    return grid;
+}
+__device__ __forceinline__ float iow_aspect(int W, int H) { return (float)W * rcp((float)H); }
+__device__ __forceinline__ float iow_px_dsx(float aspect, int W, int grid) { return aspect * rcp((float)(W * grid)); }
+__device__ __forceinline__ float iow_px_dsy(int H, int grid) { return 1.0f * rcp((float)(H * grid)); }
+__device__ __forceinline__ float iow_px_sx(float aspect, int x, int W) {
+    return (aspect * ((float)x * 2.0f - (float)W)) * rcp(2.0f * (float)W);
+}
+__device__ __forceinline__ float iow_px_sy(int y, int H) { return ((float)y * 2.0f - (float)H) * rcp(2.0f * (float)H); }
+
 }  // namespace rtk

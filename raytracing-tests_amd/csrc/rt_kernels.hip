@@ -346,22 +346,6 @@ __device__ __forceinline__ void write_px(const Frame &f, const UnitPix &p, f3 c,
     if (f.out_depth) f.out_depth[p.out] = depth;
 }
 
-// Camera ray of sample s of a pixel, out_Pixel 03...glsl:370-406
-struct IowPixelCam { float sx, sy; };
-__device__ __forceinline__ void iow_camera_ray(const IowScene &S, const Frame &f, float sx, float sy, float dsx,
-                                               float dsy, int s, f3 &ro, f3 &rd) {
-    const f3 D = mk(f.dir[0], f.dir[1], f.dir[2]), P = mk(f.pos[0], f.pos[1], f.pos[2]);
-    const f3 up = f3{0, 1, 0};
-    f3 look_at = P + D * f.focus;
-    f3 cr = cross(D, up), cu = cross(cr, D);
-    const int ix = S.ring[2 * s], iy = S.ring[2 * s + 1];
-    float rx = (S.sunflower[2 * s] * f.aperture) * 0.5f, ry = (S.sunflower[2 * s + 1] * f.aperture) * 0.5f;
-    ro = (P + cr * rx) + cu * ry;
-    f3 ld = normalize(look_at - ro);
-    f3 r_ = cross(ld, up), u_ = cross(cr, ld);
-    rd = normalize((ld * f.screen_dist + r_ * (sx + dsx * (float)ix)) + u_ * (sy + dsy * (float)iy));
-}
-
 // wave-aggregated slot allocation for parking (same ballot / popcount / rank scheme)
 __device__ __forceinline__ uint32_t park_slot(unsigned *count, bool need) {
     const unsigned long long mask = __ballot(need);
@@ -402,8 +386,8 @@ __device__ __forceinline__ void iow03_body(const Frame &f, const IowScene &S, co
     int grid = 1;
     while (grid * grid < spp) grid++;
     const float aspect = (float)W * rcp((float)H);
-    const float dsx = aspect * rcp((float)(W * grid));
-    const float dsy = 1.0f * rcp((float)(H * grid));
+    const float dsx = iow_px_dsx(aspect, W, grid);
+    const float dsy = iow_px_dsy(H, grid);
     bool live = true;     // lane may still find work
     bool busy = false;    // lane owns a pixel
     UnitPix px{};
@@ -428,8 +412,8 @@ __device__ __forceinline__ void iow03_body(const Frame &f, const IowScene &S, co
                 if constexpr (NARROW)
                     for (int e = 0; e < kIowStack; e++) K.set_bounced(e, __float_as_int(fl[kFl + e]));
                 px = unit_pixel(f, unit);
-                sx = (aspect * ((float)px.x * 2.0f - (float)W)) * rcp(2.0f * (float)W);
-                sy = ((float)px.y * 2.0f - (float)H) * rcp(2.0f * (float)H);
+                sx = iow_px_sx(aspect, px.x, W);
+                sy = iow_px_sy(px.y, H);
                 busy = true;
             } else {
                 unit = ch.order ? ch.order[q] : q;
@@ -439,8 +423,8 @@ __device__ __forceinline__ void iow03_body(const Frame &f, const IowScene &S, co
                     if (ch.cost) ch.cost[unit] = 0;
                 } else {
                     busy = true;
-                    sx = (aspect * ((float)px.x * 2.0f - (float)W)) * rcp(2.0f * (float)W);
-                    sy = ((float)px.y * 2.0f - (float)H) * rcp(2.0f * (float)H);
+                    sx = iow_px_sx(aspect, px.x, W);
+                    sy = iow_px_sy(px.y, H);
                     s = ch.per_unit_begin ? __float_as_int(ch.state[2 * (size_t)unit].w) : ch.s_begin;
                     K.size = 0;
                     urays = 0;
@@ -636,8 +620,8 @@ __device__ __forceinline__ void iow03s_body(const Frame &f, const IowScene &S, c
     int grid = 1;
     while (grid * grid < spp) grid++;
     const float aspect = (float)W * rcp((float)H);
-    const float dsx = aspect * rcp((float)(W * grid));
-    const float dsy = 1.0f * rcp((float)(H * grid));
+    const float dsx = iow_px_dsx(aspect, W, grid);
+    const float dsy = iow_px_dsy(H, grid);
     bool live = true, busy = false;
     bool solo = false;  // wave-uniform: the wave holds one unit from the sorted head
     const uint32_t solo_n = min(min(ct.solo_n, n_waves), total);
@@ -681,8 +665,8 @@ __device__ __forceinline__ void iow03s_body(const Frame &f, const IowScene &S, c
         sample = f3{0, 0, 0};
         K.size = 0; K.wmask = 0; K.rmask = 0;
         K.at(0, 7) = 0.0f; K.at(1, 7) = a.x; K.at(2, 7) = a.y; K.at(3, 7) = a.z;
-        const float sx = (aspect * ((float)px.x * 2.0f - (float)W)) * rcp(2.0f * (float)W);
-        const float sy = ((float)px.y * 2.0f - (float)H) * rcp(2.0f * (float)H);
+        const float sx = iow_px_sx(aspect, px.x, W);
+        const float sy = iow_px_sy(px.y, H);
         f3 ro, rd;
         iow_camera_ray(S, f, sx, sy, dsx, dsy, s, ro, rd);
         if (f.show_normal) {  // one ray, no stack: the normal is the sample

@@ -441,6 +441,19 @@ int iow_paths_blocks_per_cu(bool ln);
 // k_iow_paths' {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} (hipFuncGetAttributes)
 hipError_t iow_paths_kernel_info(bool ln, int info[4]);
 int iow_paths_max_blocks(int blocks);  // rt_debug_path_iow_max_blocks: cap the grid (0 = off); the previous cap
+// rt_pixels.hip: the camera rays of samples [s0, s0 + ns) of `pixels` (x, y pairs) as path-query
+// records, record k * ns + j = pixel k, sample s0 + j; n = pixels * ns <= 2^31 records (2 float4 each
+// on an INW scene, 3 on an IOW-03 one).  f: make_frame's (W, H, spp, the camera, screen_dist).
+hipError_t launch_camera_rays(const Frame &f, const InwScene &sc, const int2 *pixels, uint32_t n, uint32_t s0,
+                              uint32_t ns, float4 *rays, hipStream_t s);
+hipError_t launch_camera_rays(const Frame &f, const IowScene &sc, const int2 *pixels, uint32_t n, uint32_t s0,
+                              uint32_t ns, float4 *rays, hipStream_t s);
+// ... and the fold of f.spp path answers per pixel (samples: pixel-major) into one rt_pixel_out (2 float4) each
+hipError_t launch_pixel_fold(const Frame &f, bool iow, const int2 *pixels, uint32_t n_pixels, const float4 *samples,
+                             float4 *out, hipStream_t s);
+// {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of k_camera_rays (which = 0 INW, 1
+// IOW-03) and k_pixel_fold (2 INW, 3 IOW-03)
+hipError_t pixels_kernel_info(int which, int info[4]);
 // resident blocks per CU of the render kernel for `kind` (3 = IOW-03 wide, 4 = IOW-03 narrow,
 // 11/14 = INW layout 1/4)
 int resident_blocks_per_cu(int kind);  // 5 = sample-parallel IOW-03, 6/7 = sample-parallel INW 1/4,

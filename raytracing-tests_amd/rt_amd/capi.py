@@ -216,6 +216,17 @@ SIGNATURES = {
                                 C.c_void_p, C.c_int, C.POINTER(RtStats)]),
     "rt_debug_path_iow_kernel": (C.c_int, [C.c_int, _IP]),
     "rt_debug_path_iow_max_blocks": (C.c_int, [C.c_int]),
+    "rt_camera_rays_async": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_void_p, C.c_uint32,
+                                       C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_pixel_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32]),
+    "rt_pixel_query_async": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rt_pixels_inw": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtTexture), C.c_int,
+                                C.POINTER(RtCamera), C.POINTER(RtParams), C.c_void_p, C.c_uint32, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RtStats)]),
+    "rt_pixels_iow03": (C.c_int, [_FP, _FP, C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_void_p,
+                                  C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RtStats)]),
+    "rt_debug_pixels_kernel": (C.c_int, [C.c_int, _IP]),
     "rt_render_multi_async": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
@@ -725,6 +736,111 @@ def path_iow_kernel_info(lds: bool = True) -> dict:
     """rt_debug_path_iow_kernel: the IOW-03 path-query kernel's registers, scratch, LDS and resident blocks per CU."""
     info = (C.c_int * 4)()
     check(load().rt_debug_path_iow_kernel(int(lds), info), "rt_debug_path_iow_kernel")
+    return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
+
+
+# -------------------------------------------------------------------- pixel queries
+# rt_pixel / rt_pixel_out (include/rt_hip.h), 8 and 32 bytes
+PIXEL_DTYPE = np.dtype([("x", np.int32), ("y", np.int32)])
+PIXEL_OUT_DTYPE = np.dtype([("rgba", np.float32, 4), ("depth", np.float32), ("segments", np.uint32),
+                            ("drops", np.uint32), ("nans", np.uint32)])
+
+
+def as_pixels(pixels) -> np.ndarray:
+    """PIXEL_DTYPE records from such records or from (n, 2) integer (x, y) pairs."""
+    a = np.asarray(pixels)
+    if a.dtype != PIXEL_DTYPE:
+        xy = np.ascontiguousarray(a, np.int32).reshape(-1, 2)
+        a = np.zeros(len(xy), PIXEL_DTYPE)
+        a["x"], a["y"] = xy[:, 0], xy[:, 1]
+    return np.ascontiguousarray(a.reshape(-1))
+
+
+def dev_scene(sc: Scene, spp: int | None = None, device: int = -1):
+    """A device scene (rt_dev_scene_iow03 / rt_dev_scene_inw_tex) of a packed scene with its lights and
+    textures; free it with load().rt_dev_scene_free."""
+    lib = load()
+    spp = int(sc.params.spp if spp is None else spp)
+    if sc.stage == RT_STAGE_IOW03:
+        s = lib.rt_dev_scene_iow03(fptr(sc.types), fptr(sc.records), sc.n, spp, device)
+    else:
+        lights = sc.lights if sc.lights is not None and len(sc.lights) else None
+        tex = getattr(sc, "textures", None) or []
+        arr, keep = texture_array(tex)
+        s = lib.rt_dev_scene_inw_tex(fptr(sc.geom), sc.n, sc.layout, fptr(sc.nodes), fptr(lights), sc.n_lights,
+                                     arr if tex else None, len(tex), spp, device)
+        del keep
+    if not s:
+        raise RuntimeError("device scene creation failed")
+    return s
+
+
+def camera_rays(sc: Scene, pixels, s0: int = 0, ns: int | None = None, params: RtParams | None = None):
+    """rt_camera_rays_async through torch device buffers on the current stream: the camera rays of samples
+    [s0, s0 + ns) (default: to spp) of `pixels` ((n, 2) (x, y) pairs or PIXEL_DTYPE) of the frame
+    (sc.camera, params), pixel-major.  Returns PATH_RAY_DTYPE records (INW) or PATH_IOW_RAY_DTYPE (IOW-03)."""
+    import torch
+    lib = load()
+    p = params or sc.params
+    px = as_pixels(pixels)
+    ns = int(p.spp - s0 if ns is None else ns)
+    dtype = PATH_IOW_RAY_DTYPE if sc.stage == RT_STAGE_IOW03 else PATH_RAY_DTYPE
+    n = len(px) * ns
+    s = dev_scene(sc, p.spp)
+    try:
+        dev = torch.device("cuda")
+        d_px = torch.from_numpy(np.frombuffer(px.tobytes() + bytes(8), np.uint8).copy()).to(dev)
+        d_rays = torch.zeros(max(n, 1) * dtype.itemsize, dtype=torch.uint8, device=dev)
+        check(lib.rt_camera_rays_async(s, C.byref(sc.camera), C.byref(p), d_px.data_ptr(), len(px), int(s0), ns,
+                                       d_rays.data_ptr(), torch.cuda.current_stream().cuda_stream),
+              "rt_camera_rays_async")
+        torch.cuda.synchronize()
+        return d_rays.cpu().numpy()[: n * dtype.itemsize].view(dtype)
+    finally:
+        lib.rt_dev_scene_free(s)
+
+
+def pixels(sc: Scene, pixels, want_rays: bool = False, want_samples: bool = False, params: RtParams | None = None,
+           device: int = -1) -> dict:
+    """rt_pixels_inw / rt_pixels_iow03: the blocking pixel query of `pixels` ((n, 2) (x, y) pairs or
+    PIXEL_DTYPE) of the frame (sc.camera, params).  Returns {"pixels": PIXEL_OUT_DTYPE records, "stats":
+    dict, and when asked for "rays" / "samples": (n, spp) path-query records / answers}."""
+    lib = load()
+    p = params or sc.params
+    px = as_pixels(pixels)
+    iow = sc.stage == RT_STAGE_IOW03
+    n = len(px)
+    out = np.zeros(n, PIXEL_OUT_DTYPE)
+    rays = np.zeros((n, p.spp), PATH_IOW_RAY_DTYPE if iow else PATH_RAY_DTYPE) if want_rays else None
+    samples = np.zeros((n, p.spp), PATH_IOW_OUT_DTYPE if iow else PATH_OUT_DTYPE) if want_samples else None
+    st = RtStats()
+    tail = (C.byref(sc.camera), C.byref(p), px.ctypes.data if n else None, n,
+            rays.ctypes.data if want_rays else None, samples.ctypes.data if want_samples else None,
+            out.ctypes.data if n else None, device, C.byref(st))
+    if iow:
+        check(lib.rt_pixels_iow03(fptr(sc.types), fptr(sc.records), sc.n, *tail), "rt_pixels_iow03")
+    else:
+        lights = sc.lights if sc.lights is not None and len(sc.lights) else None
+        tex = getattr(sc, "textures", None) or []
+        arr, keep = texture_array(tex)
+        check(lib.rt_pixels_inw(fptr(sc.geom), sc.n, sc.layout, fptr(sc.nodes), fptr(lights), sc.n_lights,
+                                arr if tex else None, len(tex), *tail), "rt_pixels_inw")
+        del keep
+    res = {"pixels": out, "stats": st.as_dict()}
+    if want_rays:
+        res["rays"] = rays
+    if want_samples:
+        res["samples"] = samples
+    return res
+
+
+PIXELS_KERNELS = ("k_camera_rays INW", "k_camera_rays IOW-03", "k_pixel_fold INW", "k_pixel_fold IOW-03")
+
+
+def pixels_kernel_info(which: int) -> dict:
+    """rt_debug_pixels_kernel: registers, scratch, LDS and resident blocks per CU of PIXELS_KERNELS[which]."""
+    info = (C.c_int * 4)()
+    check(load().rt_debug_pixels_kernel(int(which), info), "rt_debug_pixels_kernel")
     return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
 
 
