@@ -318,6 +318,40 @@ void rt_dev_scene_free(rt_dev_scene *s);
  * RT_E_ARG until a later update succeeds. */
 int rt_dev_scene_inw_update(rt_dev_scene *s, const float *geom, uint32_t n, const float *nodes, const float *aabbs,
                             const float *lights, uint32_t n_lights, double timing_ms[4]);
+/* The next edit of an IOW-03 scene (the reference's stage is an editor: every ImGui edit of an object
+ * runs CopyObjBuffer and restarts the spiral, 03_Shadows_and_Materials/materials.cpp:77-152, :329-364)
+ * on the scene's existing device buffers: new hot and cold records, the RI priors, the object boxes and
+ * the culling BVH.  types: n; records: n*24; n may be the same, larger or smaller.  spp, the sample
+ * tables, the workspaces and the speculation records are kept.  Synchronises the device first; all of
+ * its device work has finished when it returns, so a render on any stream (a non-blocking one
+ * included) may follow at once.
+ * After it the scene behaves as a fresh scene of the new records would: every render
+ * (rt_render_image_async, rt_render_tiles_async, rt_render_spiral_async, with iow_spec 0 and 1) and
+ * every query (rt_trace_iow_rays_async, rt_path_iow_rays_async, rt_camera_rays_async,
+ * rt_pixel_query_async) returns, bit for bit, what rt_dev_scene_iow03(types, records, n, spp) with the
+ * same options returns, for every option.  Counters [0], [4] and [5] are the fresh scene's too; [1]
+ * and [2] are this build's own, as everywhere: the fresh scene's with RT_UPDATE_HOST_BUILD, possibly
+ * others with the device build.
+ * flags: 0 is the library's choice -- the device build from 1024 objects on, the host build below
+ * (measured, DESIGN.md §5.12: the device build is the faster one from 485 objects on, 0.35 against
+ * 0.48 ms there and 0.76 against 28.3 ms at 16383, but at 486 objects its binned tree slowed the C2
+ * frame by 2.1%, more than the build saves; a host that renders long frames of a large scene may
+ * prefer RT_UPDATE_HOST_BUILD); RT_UPDATE_HOST_BUILD or RT_UPDATE_DEVICE_BUILD forces one builder; both together,
+ * or any other bit, is RT_E_ARG.  The [build] options keep the values the scene was built with: a
+ * scene created with iow_linear = 1 keeps the linear loop and builds nothing.  n < 2 or n >= 16384
+ * means no BVH, as for a fresh scene.  A device build that runs past its level cap, or meets a box
+ * that is not finite, is redone by the host builder.
+ * timing_ms (may be NULL) receives the host time of {records and priors with their uploads; boxes
+ * and culling BVH; upload of host-built structures, 0 for the device build; the whole call}.
+ * RT_E_ARG for a null scene, null types or records, n == 0 or bad flags, and RT_E_UNSUPPORTED for an
+ * INW scene, come back before a device is touched, the scene untouched and still valid.  If a later
+ * step fails the scene keeps its previous object count but its buffers may be partly replaced: every
+ * render and query of it then returns RT_E_ARG until a later update succeeds.  Calls on one scene
+ * must not overlap its renders or queries. */
+#define RT_UPDATE_HOST_BUILD   1   /* culling BVH by rtamd::iow_cull_build, as rt_dev_scene_iow03 builds it */
+#define RT_UPDATE_DEVICE_BUILD 2   /* culling BVH built on the device */
+int rt_dev_scene_iow03_update(rt_dev_scene *s, const float *types, const float *records /* N*24 */,
+                              uint32_t n, int flags, double timing_ms[4]);
 /* Replace the scene's options (the [build] ones keep the values the scene was built with). */
 int rt_dev_scene_set_options(rt_dev_scene *s, const rt_options *o);
 
@@ -402,9 +436,10 @@ int rt_trace_inw(const float *geom, uint32_t n, int layout, const float *nodes, 
  *   - counters: [0] += n_rays; [1], [2] the node visits and object tests of the searches that ran
  *     (they depend on the options); [3], [4], [5] untouched.
  * Returns RT_E_ARG for a null scene, null rays or hits with n_rays > 0, a flag bit other than
- * RT_TRACE_ANY or n_rays > 2^31; RT_E_UNSUPPORTED for an INW scene; n_rays == 0 returns RT_OK and
- * launches nothing.  Every argument error comes back before a device is touched.  Calls on one
- * scene must not overlap each other or its renders (they share the scene's work queue). */
+ * RT_TRACE_ANY, n_rays > 2^31 or a scene a failed rt_dev_scene_iow03_update left broken;
+ * RT_E_UNSUPPORTED for an INW scene; n_rays == 0 returns RT_OK and launches nothing.  Every
+ * argument error comes back before a device is touched.  Calls on one scene must not overlap each
+ * other or its renders (they share the scene's work queue). */
 /* Device pointers (16-byte aligned); never allocates or synchronises. */
 int rt_trace_iow_rays_async(rt_dev_scene *s, const rt_ray *d_rays, uint32_t n_rays, int flags,
                             rt_hit *d_hits, uint64_t *d_counters /* 6 x u64, added to; may be NULL */, void *stream);
@@ -502,10 +537,11 @@ int rt_path_inw(const float *geom, uint32_t n, int layout, const float *nodes, c
  *   - counters: [0] += segments, [4] += dropped pushes, [5] += NaN directions, as the reference
  *     counts them; [1], [2] this build's own node visits and object tests; [3] untouched.
  * Returns RT_E_ARG for a null scene (even with n_rays == 0), null rays or out with n_rays > 0,
- * chain == 0, flags != 0 (reserved), max_bounces < 0 or n_rays > 2^31; RT_E_UNSUPPORTED for an INW
- * scene; n_rays == 0 returns RT_OK and launches nothing.  Every argument error comes back before a
- * device is touched, with the output untouched.  Calls on one scene must not overlap each other,
- * its renders or its ray queries. */
+ * chain == 0, flags != 0 (reserved), max_bounces < 0, n_rays > 2^31 or a scene a failed
+ * rt_dev_scene_iow03_update left broken; RT_E_UNSUPPORTED for an INW scene; n_rays == 0 returns RT_OK
+ * and launches nothing.  Every argument error comes back before a device is touched, with the
+ * output untouched.  Calls on one scene must not overlap each other, its renders or its ray
+ * queries. */
 typedef struct rt_path_iow_ray { float o[3]; uint32_t sample; float d[3]; uint32_t pad; float ri_in[4]; } rt_path_iow_ray;   /* 48 B */
 typedef struct rt_path_iow_out { float rgb[3]; uint32_t stale; uint32_t segments, drops, nans, status; float ri_out[4]; } rt_path_iow_out; /* 48 B */
 /* Device pointers (16-byte aligned); never allocates or synchronises, so it is graph-capturable

@@ -105,9 +105,10 @@ int rt_debug_kernel_time(rt_dev_scene *s, double *ms_total, int *launches);
  * depth-first ranks (invert 0, then 1) when the wide walk is built.  Lets the tests compare the
  * device build (rt_dev_scene_inw_update) with the host build of a fresh scene. */
 int rt_debug_wide_info(rt_dev_scene *s, uint32_t info[8], uint32_t *rank_out);
-/* Test hook: the device build of the walk structures (rt_dev_scene_inw_update) launches at most
- * `levels` SAH / collapse levels (0 = its own cap, 256); a deeper tree is built on the host instead
- * (rt_debug_wide_info info[7] = 2), which lets a test reach that fallback with an ordinary scene. */
+/* Test hook: the device build of the walk structures (rt_dev_scene_inw_update) and of the IOW-03
+ * culling BVH (rt_dev_scene_iow03_update) launches at most `levels` SAH / collapse levels (0 = its own
+ * cap, 256); a deeper tree is built on the host instead (rt_debug_wide_info info[7] = 2,
+ * rt_debug_iow_info info[3] = 2), which lets a test reach that fallback with an ordinary scene. */
 int rt_debug_build_level_cap(int levels);
 /* Test hooks for the host build of the time-bin culling trees and the sphere records (no device;
  * DESIGN.md §5.2).  rt_debug_time_bins builds the wide walk's trees from the reference's LBVH nodes
@@ -151,6 +152,15 @@ int rt_debug_inw_host_dump(const float *nodes, uint32_t n, uint32_t info[8], flo
  * the kernels read them ((lo xyz, hi x) per object, then (hi y, hi z) per object). */
 int rt_debug_iow_host_dump(const float *types, const float *records, uint32_t n, uint32_t info[4], float *wide,
                            float *obox);
+/* The IOW-03 scene's culling structures: info = {objects, wide nodes (0 = linear loop), wide depth,
+ * where built (0 host, 1 device, 2 host after the device build ran past its level cap, 3 host because
+ * a box was not finite), the LDS-staged kernel instances apply (0/1), successful
+ * rt_dev_scene_iow03_update calls so far, 0, 0}.  No device work. */
+int rt_debug_iow_info(rt_dev_scene *s, uint32_t info[8]);
+/* The scene's culling BVH and object boxes as the kernels read them (synchronises), in exactly the
+ * layout of rt_debug_iow_host_dump: info = {wide nodes (0: linear loop), 0, 0, 0}; wide and obox may
+ * be NULL.  (rt_debug_walk_dump keeps refusing IOW-03 scenes.) */
+int rt_debug_iow_dump(rt_dev_scene *s, uint32_t info[4], float *wide, float *obox);
 /* The ray-query kernel (rt_trace_rays_async) as the loaded code object has it: info = {VGPRs,
  * scratch bytes per lane, static LDS bytes per block, resident 256-lane blocks per CU} of the
  * closest-hit (any = 0) or RT_TRACE_ANY instance, with the fused cull or without.  Needs a device. */

@@ -10,6 +10,8 @@
 //     kernels walk, one level per launch, numbered breadth first (top levels first: the LDS
 //     staging takes the first nodes);
 //   - the surrounding-RI grid (counts, scan, fill).
+// The same SAH levels and collapse build the IOW-03 culling BVH of a scene update
+// (iow_cull_build_device) over boxes made from the hot records (k_iow_boxes).
 // The host path (rtamd::inw_wide_build: a full-sweep SAH) stays for fresh scenes; binned with 32
 // bins its SAH cost over the C3 leaf boxes is within 0.3% of the sweep's (16.80 against 16.75).
 // Every structure is a culling or bookkeeping structure: the walks' results do not depend on
@@ -466,12 +468,14 @@ __global__ __launch_bounds__(kB) void k_sah_level(const uint4 *tin, const uint32
 // box at 1e30 with link 1e9, culled by every ray).  Numbering breadth first without a node
 // counter: level wl + 1's wide nodes follow all earlier levels' (the prefix of the level counts),
 // in the order of their task slots; a wave takes its slots with one atomic.  meta[1] sums the
-// wide nodes (the root counted by the caller).
+// wide nodes (the root counted by the caller).  NF4 = float4 per wide node: 10 is the INW node above,
+// 8 the IOW-03 node (the six planes, the links, one unused float4; rtamd::iow_cull_build).
 __device__ __forceinline__ float bin_area(const float *bin, int i) {
     const float *b = bin + (size_t)i * 8;
     const float dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2];
     return dx * dy + dy * dz + dz * dx;
 }
+template <int NF4>
 __global__ __launch_bounds__(kB) void k_collapse_level(const uint2 *tin, uint32_t *wlvl_cnt, int wl, uint2 *tout,
                                                        const float *bin, float4 *wnodes, uint32_t *meta) {
     const uint32_t t = blockIdx.x * kB + threadIdx.x, lane = threadIdx.x & 63u;
@@ -541,10 +545,51 @@ __global__ __launch_bounds__(kB) void k_collapse_level(const uint2 *tin, uint32_
             lk[k] = (int)w + 1;
         }
     }
-    float4 *o = wnodes + (size_t)tk.y * 10;
+    float4 *o = wnodes + (size_t)tk.y * NF4;
     for (int a = 0; a < 6; a++) o[a] = make_float4(pl[a][0], pl[a][1], pl[a][2], pl[a][3]);
-    for (int a = 0; a < 3; a++) o[6 + a] = o[a];
-    o[9] = make_float4(__int_as_float(lk[0]), __int_as_float(lk[1]), __int_as_float(lk[2]), __int_as_float(lk[3]));
+    const float4 links = make_float4(__int_as_float(lk[0]), __int_as_float(lk[1]), __int_as_float(lk[2]), __int_as_float(lk[3]));
+    if constexpr (NF4 == 10) {
+        for (int a = 0; a < 3; a++) o[6 + a] = o[a];
+        o[9] = links;
+    } else {
+        static_assert(NF4 == 8, "the INW (10) or the IOW-03 (8) wide node");
+        o[6] = links;
+        o[7] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
+// IOW-03: every object's culling box from its hot record (pos3 type M9 scale3 ...), by the statements
+// of rtamd::iow_cull_build in their order (|M^T| times the local half extents, inflated; plain IEEE
+// operations under -ffp-contract=off, so the boxes equal the host's bit for bit): obox as the kernels
+// read it, and the SAH build's box / cen / ids.  meta[0] is set when some box value is not finite.
+__global__ __launch_bounds__(kB) void k_iow_boxes(const float *hot, uint32_t n, float4 *obox, float *box, float *cen,
+                                                  uint32_t *ids, uint32_t *meta) {
+    const uint32_t j = blockIdx.x * kB + threadIdx.x;
+    if (j >= n) return;  // no cross-lane work in this kernel
+    const float *r = hot + (size_t)j * kIowHot;
+    const bool ell = (int)r[3] == RT_IOW_ELLIPSOID;
+    float h[3];
+    for (int k = 0; k < 3; k++) h[k] = fabsf(r[13 + k]) * (ell ? 1.0f : 0.5f);
+    const float big = fmaxf(fabsf(r[0]), fmaxf(fabsf(r[1]), fabsf(r[2])));
+    float b[6];
+    bool fin = true;
+    for (int k = 0; k < 3; k++) {
+        const float *col = r + 4 + 3 * k;  // column k of M
+        float e = fabsf(col[0]) * h[0] + fabsf(col[1]) * h[1] + fabsf(col[2]) * h[2];
+        e = e * 1.001f + 1e-3f + big * 1e-5f;
+        b[k] = r[k] - e;
+        b[3 + k] = r[k] + e;
+        fin = fin && isfinite(b[k]) && isfinite(b[3 + k]);
+    }
+    obox[j] = make_float4(b[0], b[1], b[2], b[3]);
+    reinterpret_cast<float2 *>(obox + n)[j] = make_float2(b[4], b[5]);
+    for (int k = 0; k < 3; k++) {
+        box[6 * j + k] = b[k];
+        box[6 * j + 3 + k] = b[3 + k];
+        cen[3 * j + k] = 0.5f * (b[k] + b[3 + k]);
+    }
+    ids[j] = j;
+    if (!fin) atomicOr(meta, 1u);
 }
 
 // ---- surrounding-RI grid (rtamd::ri_grid_build): bounds, per-cell counts, offsets, ids
@@ -730,26 +775,24 @@ size_t inw_build_workspace_bytes(uint32_t n) { return n ? carve(reinterpret_cast
         if (e_ != hipSuccess) return e_;                                                  \
     } while (0)
 
-hipError_t inw_wide_build_device(const float4 *nodes, const uint32_t *lcnt, uint32_t n, void *ws, size_t ws_bytes,
-                                 InwWideDev &out, hipStream_t s, int max_levels) {
-    const int lvl_cap = max_levels > 0 && max_levels < kMaxLevels ? max_levels : kMaxLevels;
-    if (n < 2 || !nodes || !lcnt || !ws || ws_bytes < inw_build_workspace_bytes(n) || !out.wnodes || !out.rank || !out.leafbox)
-        return hipErrorInvalidValue;
-    BuildWs w;
-    carve(ws, n, &w);
-    const uint32_t nn = 2 * n - 1;
+// The level loops both families share: the binary SAH tree over w.box / w.cen / w.ids (one k_sah_level
+// launch per level) and its 4-wide collapse into wnodes (NF4 float4 per node, one k_collapse_level
+// launch per level).  The pending-task counts are read back every few levels; the last read brings
+// the counters (meta: [0] the caller's flag word, [1] wide nodes, [2], [3] the INW walk's high-water
+// mark and wbound) and w.ri_bnd along.  hipErrorNotSupported: deeper than lvl_cap.
+struct BuildLevels {
+    int depth;
+    uint32_t meta[4], bnd[6];
+};
+static int level_cap(int max_levels) { return max_levels > 0 && max_levels < kMaxLevels ? max_levels : kMaxLevels; }
+static hipError_t build_begin(const BuildWs &w, hipStream_t s) {
     BUILD_HIP(hipMemsetAsync(w.meta, 0, 16 * 4, s));
     BUILD_HIP(hipMemsetAsync(w.lvl_cnt, 0, (kMaxLevels + 1) * 4, s));
     BUILD_HIP(hipMemsetAsync(w.wlvl_cnt, 0, (kMaxLevels + 1) * 4, s));
-    hipLaunchKernelGGL(k_leaves, dim3(nblk(nn)), dim3(kB), 0, s, nodes, nn, n, out.leafbox, w.box, w.cen, w.leafnode,
-                       w.ids, w.meta);
-    hipLaunchKernelGGL(k_ranks, dim3(nblk(n)), dim3(kB), 0, s, nodes, n, w.leafnode, lcnt, out.rank);
-    hipLaunchKernelGGL(k_high, dim3(nblk(nn)), dim3(kB), 0, s, nodes, nn, w.meta);
-    // the RI grid's bounds (the leaf boxes'), read back with the counts below
-    const uint32_t binit[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    BUILD_HIP(hipMemcpyAsync(w.ri_bnd, binit, sizeof(binit), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_ri_bounds, dim3(nblk(n)), dim3(kB), 0, s, out.leafbox, n, w.ri_bnd);
-    BUILD_HIP(hipGetLastError());
+    return hipSuccess;
+}
+template <int NF4>
+static hipError_t build_levels(const BuildWs &w, uint32_t n, float4 *wnodes, int lvl_cap, hipStream_t s, BuildLevels &out) {
     // binary SAH tree: root task (node 0, all objects, its descendants from node 1)
     const uint32_t one = 1u;
     const uint4 root = make_uint4(0u, 0u, n, 1u);
@@ -776,29 +819,73 @@ hipError_t inw_wide_build_device(const float4 *nodes, const uint32_t *lcnt, uint
     int wl = 0;
     for (;;) {
         for (int k = 0; k < kLevelBatch && wl < lvl_cap; k++, wl++)
-            hipLaunchKernelGGL(k_collapse_level, dim3(nblk(n)), dim3(kB), 0, s, w.wtask[wl & 1], w.wlvl_cnt, wl,
-                               w.wtask[(wl + 1) & 1], w.bin, out.wnodes, w.meta);
+            hipLaunchKernelGGL(k_collapse_level<NF4>, dim3(nblk(n)), dim3(kB), 0, s, w.wtask[wl & 1], w.wlvl_cnt, wl,
+                               w.wtask[(wl + 1) & 1], w.bin, wnodes, w.meta);
         BUILD_HIP(hipGetLastError());
         // this batch's level counts, the counters (meta) and the RI bounds in one read
+        // (a level cap below the batch size launches fewer levels: the read starts at level 0 then)
+        const int l0 = wl > kLevelBatch ? wl - kLevelBatch : 0, nl = wl - l0;
         uint32_t rb[kLevelBatch + 1 + 4 + 6];
-        BUILD_HIP(hipMemcpyAsync(rb, w.wlvl_cnt + wl - kLevelBatch, (kLevelBatch + 1) * 4, hipMemcpyDeviceToHost, s));
+        BUILD_HIP(hipMemcpyAsync(rb, w.wlvl_cnt + l0, (size_t)(nl + 1) * 4, hipMemcpyDeviceToHost, s));
         BUILD_HIP(hipMemcpyAsync(rb + kLevelBatch + 1, w.meta, 4 * 4, hipMemcpyDeviceToHost, s));
         BUILD_HIP(hipMemcpyAsync(rb + kLevelBatch + 5, w.ri_bnd, 6 * 4, hipMemcpyDeviceToHost, s));
         BUILD_HIP(hipStreamSynchronize(s));
-        if (rb[kLevelBatch] == 0) {
-            int d = wl - kLevelBatch;
-            while (d < wl && rb[d - (wl - kLevelBatch)] != 0) d++;
+        if (rb[nl] == 0) {
+            int d = l0;
+            while (d < wl && rb[d - l0] != 0) d++;
             out.depth = d;
-            const uint32_t *meta = rb + kLevelBatch + 1, *b = rb + kLevelBatch + 5;
-            out.n_wnodes = meta[1];
-            out.dfs_high = meta[2] ? meta[2] : 1u;
-            out.wbound = __builtin_bit_cast(float, meta[3]);
-            auto dec = [](uint32_t u) { return __builtin_bit_cast(float, (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); };
-            for (int a = 0; a < 3; a++) { out.ri_lo[a] = dec(b[a]); out.ri_hi[a] = dec(b[3 + a]); }
+            for (int k = 0; k < 4; k++) out.meta[k] = rb[kLevelBatch + 1 + k];
+            for (int k = 0; k < 6; k++) out.bnd[k] = rb[kLevelBatch + 5 + k];
             break;
         }
         if (wl >= lvl_cap) return hipErrorNotSupported;
     }
+    return hipSuccess;
+}
+
+hipError_t inw_wide_build_device(const float4 *nodes, const uint32_t *lcnt, uint32_t n, void *ws, size_t ws_bytes,
+                                 InwWideDev &out, hipStream_t s, int max_levels) {
+    const int lvl_cap = level_cap(max_levels);
+    if (n < 2 || !nodes || !lcnt || !ws || ws_bytes < inw_build_workspace_bytes(n) || !out.wnodes || !out.rank || !out.leafbox)
+        return hipErrorInvalidValue;
+    BuildWs w;
+    carve(ws, n, &w);
+    const uint32_t nn = 2 * n - 1;
+    BUILD_HIP(build_begin(w, s));
+    hipLaunchKernelGGL(k_leaves, dim3(nblk(nn)), dim3(kB), 0, s, nodes, nn, n, out.leafbox, w.box, w.cen, w.leafnode,
+                       w.ids, w.meta);
+    hipLaunchKernelGGL(k_ranks, dim3(nblk(n)), dim3(kB), 0, s, nodes, n, w.leafnode, lcnt, out.rank);
+    hipLaunchKernelGGL(k_high, dim3(nblk(nn)), dim3(kB), 0, s, nodes, nn, w.meta);
+    // the RI grid's bounds (the leaf boxes'), read back with the counts below
+    const uint32_t binit[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+    BUILD_HIP(hipMemcpyAsync(w.ri_bnd, binit, sizeof(binit), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ri_bounds, dim3(nblk(n)), dim3(kB), 0, s, out.leafbox, n, w.ri_bnd);
+    BUILD_HIP(hipGetLastError());
+    BuildLevels r;
+    BUILD_HIP(build_levels<10>(w, n, out.wnodes, lvl_cap, s, r));
+    out.depth = r.depth;
+    out.n_wnodes = r.meta[1];
+    out.dfs_high = r.meta[2] ? r.meta[2] : 1u;
+    out.wbound = __builtin_bit_cast(float, r.meta[3]);
+    auto dec = [](uint32_t u) { return __builtin_bit_cast(float, (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); };
+    for (int a = 0; a < 3; a++) { out.ri_lo[a] = dec(r.bnd[a]); out.ri_hi[a] = dec(r.bnd[3 + a]); }
+    return hipSuccess;
+}
+
+hipError_t iow_cull_build_device(const float *hot, uint32_t n, void *ws, size_t ws_bytes, float4 *wide, float4 *obox,
+                                 IowCullDev &out, hipStream_t s, int max_levels) {
+    if (n < 2 || n >= 16384 || !hot || !ws || ws_bytes < inw_build_workspace_bytes(n) || !wide || !obox)
+        return hipErrorInvalidValue;
+    BuildWs w;
+    carve(ws, n, &w);
+    BUILD_HIP(build_begin(w, s));
+    hipLaunchKernelGGL(k_iow_boxes, dim3(nblk(n)), dim3(kB), 0, s, hot, n, obox, w.box, w.cen, w.ids, w.meta);
+    BUILD_HIP(hipGetLastError());
+    BuildLevels r;
+    BUILD_HIP(build_levels<8>(w, n, wide, level_cap(max_levels), s, r));
+    out.n_wide = r.meta[1];
+    out.depth = r.depth;
+    out.nonfinite = r.meta[0];
     return hipSuccess;
 }
 

@@ -203,6 +203,23 @@ int rt_dev_scene_inw_update(rt_dev_scene *s, const float *geom, uint32_t n, cons
     }
 }
 
+int rt_dev_scene_iow03_update(rt_dev_scene *s, const float *types, const float *records, uint32_t n, int flags,
+                              double timing_ms[4]) {
+    // argument errors come back before a device is touched, the scene untouched and still valid
+    if (!s || !types || !records || n == 0) return RT_E_ARG;
+    if ((flags & ~(RT_UPDATE_HOST_BUILD | RT_UPDATE_DEVICE_BUILD)) || flags == (RT_UPDATE_HOST_BUILD | RT_UPDATE_DEVICE_BUILD))
+        return RT_E_ARG;
+    if (s->kind != 3) return RT_E_UNSUPPORTED;
+    HIP_OK(hipSetDevice(s->device));
+    HIP_OK(hipDeviceSynchronize());  // the scene's last frame may still read the buffers being replaced
+    try {  // the host builders allocate: no exception crosses the ABI
+        return update_iow03(s, types, records, n, flags, timing_ms);
+    } catch (...) {
+        s->broken = true;
+        return RT_E_ARG;
+    }
+}
+
 int rt_dev_scene_set_options(rt_dev_scene *s, const rt_options *o) {
     if (!s || !options_ok(o)) return RT_E_ARG;
     const int wide = s->opt.inw_wide_walk, linear = s->opt.iow_linear;  // [build] options stay
@@ -557,7 +574,7 @@ int rt_trace_iow_rays_async(rt_dev_scene *s, const rt_ray *d_rays, uint32_t n_ra
                             uint64_t *d_counters, void *stream) {
     if (!s || (flags & ~RT_TRACE_ANY)) return RT_E_ARG;
     if (s->kind != 3) return RT_E_UNSUPPORTED;
-    if (n_rays > (1u << 31)) return RT_E_ARG;
+    if (s->broken || n_rays > (1u << 31)) return RT_E_ARG;
     if (n_rays == 0) return RT_OK;
     if (!d_rays || !d_hits) return RT_E_ARG;
     const rtk::IowScene sc = iow_view(*s);  // the sample tables stay unread
@@ -631,7 +648,7 @@ int rt_path_iow_rays_async(rt_dev_scene *s, const rt_path_iow_ray *d_rays, uint3
                   "rt_path_iow_ray / rt_path_iow_out are 3 float4 each");
     if (!s || flags != 0 || chain == 0 || max_bounces < 0) return RT_E_ARG;
     if (s->kind != 3) return RT_E_UNSUPPORTED;
-    if (n_rays > (1u << 31)) return RT_E_ARG;
+    if (s->broken || n_rays > (1u << 31)) return RT_E_ARG;
     if (n_rays == 0) return RT_OK;
     if (!d_rays || !d_out) return RT_E_ARG;
     const rtk::IowScene sc = iow_view(*s);

@@ -376,6 +376,30 @@ int rt_debug_iow_host_dump(const float *types, const float *records, uint32_t n,
     return RT_OK;
 }
 
+int rt_debug_iow_info(rt_dev_scene *s, uint32_t info[8]) {
+    if (!s || s->kind != 3 || !info) return RT_E_ARG;
+    const IowCullPriors &q = s->iow;
+    const rtk::IowScene sc = iow_view(*s);
+    const uint32_t v[8] = {s->n, sc.n_nodes, uint32_t(q.depth), q.built, rtk::iow_lds(sc) ? 1u : 0u, q.updates, 0u, 0u};
+    std::memcpy(info, v, sizeof(v));
+    return RT_OK;
+}
+
+int rt_debug_iow_dump(rt_dev_scene *s, uint32_t info[4], float *wide, float *obox) {
+    if (!s || s->kind != 3 || s->broken || !info) return RT_E_ARG;
+    HIP_OK(hipSetDevice(s->device));
+    HIP_OK(hipDeviceSynchronize());
+    std::memset(info, 0, 4 * sizeof(uint32_t));
+    const rtk::IowScene sc = iow_view(*s);
+    if (!sc.nodes) return RT_OK;
+    const size_t wb = size_t(sc.n_nodes) * 32 * sizeof(float), ob = size_t(s->n) * 6 * sizeof(float);
+    if (s->nodes.bytes < wb || !s->iow.obox.p || s->iow.obox.bytes < ob) return RT_E_ARG;  // never read past the allocation
+    info[0] = sc.n_nodes;
+    if (wide) HIP_OK(hipMemcpy(wide, s->nodes.p, wb, hipMemcpyDeviceToHost));
+    if (obox) HIP_OK(hipMemcpy(obox, s->iow.obox.p, ob, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 int rt_debug_trace_kernel(int any, int fused, int info[4]) {
     if (!info) return RT_E_ARG;
     HIP_OK(rtk::inw_trace_kernel_info(any != 0, fused != 0, info));

@@ -31,6 +31,12 @@ struct IowCullPriors {
     // entry, 1 for the camera ray, every material RI; 03...glsl:285-356), up to 8, else none
     float alt_vals[8] = {};
     int n_alt_vals = 0;
+    int depth = 0;           // culling BVH: levels of the 4-wide tree
+    // rt_dev_scene_iow03_update (update_iow03)
+    uint32_t built = 0;      // where the culling BVH was built: 0 host, 1 device, 2 host after the device build ran
+                             // past its level cap, 3 host because a box was not finite (rt_debug_iow_info info[3])
+    uint32_t updates = 0;    // successful updates so far
+    DevBuf build_ws;         // the device build's workspace (rt_build.hip)
 };
 
 // INW: the wide walk's structures and the surrounding-RI grid (make_inw_wide, make_inw_wide_device)
@@ -147,7 +153,8 @@ struct rt_dev_scene {
     DevBuf tex, tex_info;  // INW-04 material textures (float4 texels, (first, w, h, 0) per texture)
     uint32_t n_tex = 0;
     DevBuf walk_ctr;       // the last frame's closest-hit queries handed to the LBVH walks (u64)
-    bool broken = false;   // a failed rt_dev_scene_inw_update left the buffers inconsistent: no renders
+    bool broken = false;   // a failed rt_dev_scene_inw_update / rt_dev_scene_iow03_update left the buffers
+                           // inconsistent: no renders, no queries
     IowCullPriors iow;
     InwWalk walk;
     InwFold fold;
@@ -160,10 +167,14 @@ struct rt_dev_scene {
 };
 
 // ---------------------------------------------------------------- the kernels' scene views
+// root_link says whether the scene has a culling BVH: after an update to a scene without one the node
+// and box buffers still hold the old tree (they keep their capacity), so the kernels get null then,
+// which is what they read as "the linear loop".
 inline rtk::IowScene iow_view(const rt_dev_scene &s) {
-    return rtk::IowScene{s.hot.as<float>(), s.cold.as<float>(), s.n, s.nodes.as<float4>(),
+    const bool bvh = s.iow.root_link != 0;
+    return rtk::IowScene{s.hot.as<float>(), s.cold.as<float>(), s.n, bvh ? s.nodes.as<float4>() : nullptr,
                          s.sunflower.as<float>(), s.fib.as<float>(), s.ring.as<int>(), s.iow.root_link,
-                         s.iow.obox.as<float4>(), s.iow.n_wide, s.opt.iow_lds_bvh};
+                         bvh ? s.iow.obox.as<float4>() : nullptr, bvh ? s.iow.n_wide : 0u, s.opt.iow_lds_bvh};
 }
 
 // INW wide walk (DESIGN.md "INW wide walk").  The reference finds the closest hit by a
@@ -259,6 +270,7 @@ int make_inw(rt_dev_scene *s, const float *geom, uint32_t n, int layout, const f
              uint32_t n_lights, const rt_texture *tex, int n_tex, int spp);
 int update_inw(rt_dev_scene *s, const float *geom, uint32_t n, const float *nodes, const float *aabbs,
                const float *lights, uint32_t n_lights, double *ms);
+int update_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n, int flags, double *ms);
 bool inw_sphere_records(const float *geom, uint32_t n, int layout, std::vector<float> &out);
 bool inw_textured(const float *geom, uint32_t n, int layout);
 bool textures_ok(const rt_texture *tex, int n_tex);

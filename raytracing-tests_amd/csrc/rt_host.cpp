@@ -723,6 +723,7 @@ bool iow_cull_build(const float *types, const float *rec, uint32_t n, IowCull &o
             std::memcpy(&out.wide[w * 32 + 24 + size_t(k)], &link, sizeof(link));
         }
     out.n_wide = uint32_t(out.wide.size() / 32);
+    out.depth = depth4;
     out.obox.assign(size_t(n) * 6, 0.0f);
     for (uint32_t j = 0; j < n; j++) {
         const float *b = boxes.data() + size_t(j) * 6;

@@ -115,6 +115,7 @@ std::vector<float> bvh4_collapse(const std::vector<float> &bin, int *depth);
 struct IowCull {
     std::vector<float> wide, obox;
     uint32_t n_wide = 0;
+    int depth = 0;  // levels of the 4-wide tree
 };
 bool iow_cull_build(const float *types, const float *rec, uint32_t n, IowCull &out);
 

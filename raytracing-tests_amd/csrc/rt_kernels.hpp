@@ -328,6 +328,20 @@ size_t inw_build_workspace_bytes(uint32_t n);
 // hipErrorNotSupported (the caller then builds on the host)
 hipError_t inw_wide_build_device(const float4 *nodes, const uint32_t *lcnt, uint32_t n, void *ws, size_t ws_bytes,
                                  InwWideDev &out, hipStream_t s, int max_levels = 0);
+// The IOW-03 culling structures built on the device from the uploaded hot records (rt_build.hip,
+// DESIGN.md §5.12): the object boxes as the kernels read them (obox: n float4 (lo xyz, hi x), then n
+// float2 (hi y, hi z); bit-equal to rtamd::iow_cull_build's) and a 4-wide culling BVH over them by the
+// same binned SAH levels and collapse as the INW build (wide: 8 float4 per node, <= n nodes).
+// 2 <= n < 16384; ws holds inw_build_workspace_bytes(n).  Synchronises the stream (level counts).
+// hipErrorNotSupported: deeper than max_levels; nonfinite != 0: some box value is not finite (the
+// tree is then not to be used); in both cases the caller builds on the host.
+struct IowCullDev {
+    uint32_t n_wide;
+    int depth;
+    uint32_t nonfinite;
+};
+hipError_t iow_cull_build_device(const float *hot, uint32_t n, void *ws, size_t ws_bytes, float4 *wide, float4 *obox,
+                                 IowCullDev &out, hipStream_t s, int max_levels = 0);
 // the quantised form of nw wide nodes (InwScene::qnodes): 4 float4 per node, planes rounded
 // outward by at least `margin` beyond the wide node's (rt_build.hip)
 hipError_t inw_quantize_wnodes(const float4 *wnodes, uint32_t nw, float4 *qnodes, float margin, hipStream_t s);

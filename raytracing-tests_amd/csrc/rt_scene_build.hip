@@ -1,7 +1,7 @@
 // rt_scene_build.hip -- scene construction: converts the reference's record layouts into the
 // kernels' device layouts (hot/cold split, per-object reciprocals hoisted under the numerics
 // contract), builds the sample tables, the walk structures (host and device builds) and the
-// textures, and redoes that per redraw (update_inw).
+// textures, and redoes that per redraw (update_inw, update_iow03).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -254,8 +254,10 @@ bool textures_ok(const rt_texture *tex, int n_tex) {
     return true;
 }
 
-int make_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n, int spp) {
-    std::vector<float> hot(size_t(n) * rtk::kIowHot, 0.0f), cold(size_t(n) * rtk::kIowCold, 0.0f);
+// The kernels' hot / cold records from the reference's IOW-03 records (24 floats) and types.
+static void iow_records(const float *types, const float *rec, uint32_t n, std::vector<float> &hot, std::vector<float> &cold) {
+    hot.assign(size_t(n) * rtk::kIowHot, 0.0f);
+    cold.assign(size_t(n) * rtk::kIowCold, 0.0f);
     for (uint32_t j = 0; j < n; j++) {
         const float *r = rec + size_t(j) * 24;
         float *h = hot.data() + size_t(j) * rtk::kIowHot;
@@ -271,30 +273,39 @@ int make_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n
         static const float kI[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
         h[19] = std::memcmp(r + 3, kI, sizeof(kI)) == 0 ? 1.0f : 0.0f;
     }
+}
+
+// The RI priors of the sample-parallel pipeline: the most common RefractiveIndex (record float 20,
+// Geometry::FillBuffer materials.h:48-76) and the values a stale ray-stack RI can hold.
+static void iow_priors(const float *rec, uint32_t n, IowCullPriors &q) {
+    std::vector<float> ri(n);
+    for (uint32_t j = 0; j < n; j++) ri[j] = rec[size_t(j) * 24 + 20];
+    std::sort(ri.begin(), ri.end());
+    size_t best = 0;
+    for (size_t i = 0; i < ri.size();) {
+        size_t k = i;
+        while (k < ri.size() && ri[k] == ri[i]) k++;
+        if (k - i > best) { best = k - i; q.ri_prior = ri[i]; }
+        i = k;
+    }
+    std::vector<float> vals{0.0f, 1.0f};
+    vals.insert(vals.end(), ri.begin(), ri.end());
+    std::sort(vals.begin(), vals.end());
+    vals.erase(std::unique(vals.begin(), vals.end(), [](float a, float b) {
+        return std::memcmp(&a, &b, sizeof(a)) == 0; }), vals.end());
+    q.n_alt_vals = 0;
+    if (vals.size() <= 8) {
+        for (size_t v = 0; v < vals.size(); v++) q.alt_vals[v] = vals[v];
+        q.n_alt_vals = int(vals.size());
+    }
+}
+
+int make_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n, int spp) {
+    std::vector<float> hot, cold;
+    iow_records(types, rec, n, hot, cold);
     s->kind = 3; s->n = n;
     IowCullPriors &q = s->iow;
-    {  // most common RefractiveIndex (record float 20, Geometry::FillBuffer materials.h:48-76)
-        std::vector<float> ri(n);
-        for (uint32_t j = 0; j < n; j++) ri[j] = rec[size_t(j) * 24 + 20];
-        std::sort(ri.begin(), ri.end());
-        size_t best = 0;
-        for (size_t i = 0; i < ri.size();) {
-            size_t k = i;
-            while (k < ri.size() && ri[k] == ri[i]) k++;
-            if (k - i > best) { best = k - i; q.ri_prior = ri[i]; }
-            i = k;
-        }
-        std::vector<float> vals{0.0f, 1.0f};
-        vals.insert(vals.end(), ri.begin(), ri.end());
-        std::sort(vals.begin(), vals.end());
-        vals.erase(std::unique(vals.begin(), vals.end(), [](float a, float b) {
-            return std::memcmp(&a, &b, sizeof(a)) == 0; }), vals.end());
-        q.n_alt_vals = 0;
-        if (vals.size() <= 8) {
-            for (size_t v = 0; v < vals.size(); v++) q.alt_vals[v] = vals[v];
-            q.n_alt_vals = int(vals.size());
-        }
-    }
+    iow_priors(rec, n, q);
     HIP_OK(s->hot.upload(hot.data(), hot.size() * sizeof(float)));
     HIP_OK(s->cold.upload(cold.data(), cold.size() * sizeof(float)));
     // Culling BVH over the objects (the reference loops linearly; rtk::iow_launch_ray keeps its
@@ -304,10 +315,93 @@ int make_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n
         HIP_OK(s->nodes.upload(cull.wide.data(), cull.wide.size() * sizeof(float)));
         q.root_link = 1;
         q.n_wide = cull.n_wide;
+        q.depth = cull.depth;
         HIP_OK(q.obox.upload(cull.obox.data(), cull.obox.size() * sizeof(float)));
     }
     set_residency(s);
     return build_tables(s, spp);
+}
+
+// Objects from which the library's choice (flags = 0) builds the culling BVH on the device, read from
+// the measured rows of DESIGN.md §5.12: the device build beats the host build at every measured size
+// (0.35 against 0.48 ms at 485 objects, 0.38 against 1.03 ms at 1024), but at the C2 scene (486
+// objects) its binned tree costs the frame more than the build saves (+6.8% node visits, +2.1% frame
+// time), so that size keeps the host build and the next measured one is the threshold.
+constexpr uint32_t kIowDeviceBuildMin = 1024;
+
+// The next edit of an IOW-03 scene on its existing device buffers (rt_dev_scene_iow03_update; the
+// reference's CopyObjBuffer per ImGui edit, 03_Shadows_and_Materials/materials.cpp:329-364): new hot
+// and cold records, the RI priors, the object boxes and the culling BVH -- built on the device
+// (rtk::iow_cull_build_device) or by rtamd::iow_cull_build as make_iow03 builds it.
+// The sample tables, workspaces and speculation records stay.  ms[4]: host time of the records and
+// priors with their uploads, the boxes and the BVH, the upload of host-built structures, the call.
+int update_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n, int flags, double *ms) {
+    using clk = std::chrono::steady_clock;
+    const auto t_call = clk::now();
+    auto t = t_call;
+    auto lap = [&](int k) {
+        const auto now = clk::now();
+        if (ms) ms[k] = std::chrono::duration<double, std::milli>(now - t).count();
+        t = now;
+    };
+    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
+    // Until every step below has succeeded the buffers may hold a mix of the old and the new scene:
+    // the scene refuses renders and queries and keeps its old n and counts, so nothing indexes past
+    // a buffer.  The new sizes are committed at the end.
+    s->broken = true;
+    IowCullPriors &q = s->iow;
+    std::vector<float> hot, cold;
+    iow_records(types, rec, n, hot, cold);
+    iow_priors(rec, n, q);
+    HIP_OK(s->hot.store(hot.data(), hot.size() * sizeof(float)));
+    HIP_OK(s->cold.store(cold.data(), cold.size() * sizeof(float)));
+    lap(0);
+    // a scene created with iow_linear keeps the linear loop; n < 2 or n >= 16384 has no BVH, as
+    // rtamd::iow_cull_build decides
+    const bool bvh = !s->opt.iow_linear && n >= 2 && n < 16384;
+    const bool device_build = flags == RT_UPDATE_DEVICE_BUILD || (flags == 0 && n >= kIowDeviceBuildMin);
+    uint32_t n_wide = 0, built = 0;
+    int depth = 0;
+    bool host_build = bvh && !device_build;
+    if (bvh && device_build) {
+        HIP_OK(s->nodes.reserve(size_t(n) * 8 * sizeof(float4)));
+        HIP_OK(q.obox.reserve(size_t(n) * 6 * sizeof(float)));
+        HIP_OK(q.build_ws.reserve(rtk::inw_build_workspace_bytes(n)));
+        rtk::IowCullDev out{};
+        const hipError_t be = rtk::iow_cull_build_device(s->hot.as<float>(), n, q.build_ws.p, q.build_ws.bytes,
+                                                         s->nodes.as<float4>(), q.obox.as<float4>(), out, nullptr,
+                                                         g_build_levels);
+        // deeper than the level cap (a chain-like scene), or a box that is not finite (the binned
+        // splits mean nothing then): the host builder, whose scene equals a fresh one by construction
+        if (be == hipErrorNotSupported) { built = 2; host_build = true; }
+        else {
+            HIP_OK(be);
+            if (out.nonfinite) { built = 3; host_build = true; }
+            else { built = 1; n_wide = out.n_wide; depth = out.depth; }
+        }
+    }
+    if (host_build) {
+        rtamd::IowCull cull;
+        if (!rtamd::iow_cull_build(types, rec, n, cull)) return RT_E_ARG;  // (bvh: it builds)
+        lap(1);
+        HIP_OK(s->nodes.store(cull.wide.data(), cull.wide.size() * sizeof(float)));
+        HIP_OK(q.obox.store(cull.obox.data(), cull.obox.size() * sizeof(float)));
+        n_wide = cull.n_wide;
+        depth = cull.depth;
+        lap(2);
+    } else {
+        lap(1);
+    }
+    HIP_OK(hipDeviceSynchronize());  // every copy and build kernel: a render on any stream may follow
+    q.root_link = bvh ? 1 : 0;
+    q.n_wide = n_wide;
+    q.depth = depth;
+    q.built = built;
+    q.updates++;
+    s->n = n;
+    s->broken = false;
+    if (ms) ms[3] = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
+    return RT_OK;
 }
 
 // Sphere records (rtk::InwScene::sph) when every object is an ellipsoid with equal scales and the

@@ -182,6 +182,9 @@ SIGNATURES = {
     "rt_dev_scene_set_options": (C.c_int, [C.c_void_p, C.POINTER(RtOptions)]),
     "rt_dev_scene_inw_update": (C.c_int, [C.c_void_p, _FP, C.c_uint32, _FP, _FP, _FP, C.c_uint32,
                                           C.POINTER(C.c_double)]),
+    "rt_dev_scene_iow03_update": (C.c_int, [C.c_void_p, _FP, _FP, C.c_uint32, C.c_int, C.POINTER(C.c_double)]),
+    "rt_debug_iow_info": (C.c_int, [C.c_void_p, _U32P]),
+    "rt_debug_iow_dump": (C.c_int, [C.c_void_p, _U32P, _FP, _FP]),
     "rt_debug_path": (C.c_int, [C.c_void_p, C.POINTER(RtPathInfo)]),
     "rt_debug_wide_info": (C.c_int, [C.c_void_p, _U32P, _U32P]),
     "rt_tile_deal": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _IP, C.c_int]),
@@ -540,6 +543,49 @@ def iow_host_dump(types: np.ndarray, records: np.ndarray, n: int) -> dict | None
     raw = np.zeros(6 * n, np.float32)
     check(lib.rt_debug_iow_host_dump(fptr(types), fptr(records), n, info, fptr(wide), fptr(raw)),
           "rt_debug_iow_host_dump")
+    obox = np.concatenate([raw[:4 * n].reshape(n, 4), raw[4 * n:].reshape(n, 2)], axis=1)
+    return {"wide": wide, "obox": obox}
+
+
+RT_UPDATE_HOST_BUILD, RT_UPDATE_DEVICE_BUILD = 1, 2
+
+
+def update_iow03(handle, types: np.ndarray, records: np.ndarray, flags: int = 0) -> list:
+    """rt_dev_scene_iow03_update: the next edit of the IOW-03 device scene `handle` (new types (n) and
+    records (n, 24)); flags 0, RT_UPDATE_HOST_BUILD or RT_UPDATE_DEVICE_BUILD.  Returns timing_ms: host
+    ms of [records, boxes and culling BVH, upload of host-built structures, the whole call]."""
+    types = np.ascontiguousarray(types, np.float32)
+    records = np.ascontiguousarray(records, np.float32)
+    tm = (C.c_double * 4)()
+    check(load().rt_dev_scene_iow03_update(handle, fptr(types), fptr(records), len(types), int(flags), tm),
+          "rt_dev_scene_iow03_update")
+    return list(tm)
+
+
+IOW_INFO_KEYS = ("objects", "wide_nodes", "wide_depth", "built", "lds", "updates")
+
+
+def iow_info(handle) -> dict:
+    """rt_debug_iow_info of an IOW-03 device scene: objects, wide_nodes (0: linear loop), wide_depth, built
+    (0 host, 1 device, 2 host after the level cap, 3 host because of a non-finite box), lds (the
+    LDS-staged kernel instances apply), updates (successful updates so far)."""
+    info = (C.c_uint32 * 8)()
+    check(load().rt_debug_iow_info(handle, info), "rt_debug_iow_info")
+    return dict(zip(IOW_INFO_KEYS, (int(x) for x in info)))
+
+
+def iow_dump(handle) -> dict | None:
+    """rt_debug_iow_dump: the culling BVH and object boxes of an IOW-03 device scene as its kernels read
+    them, in iow_host_dump's keys (wide (N, 32), obox (n, 6)).  None: no BVH (the linear loop)."""
+    lib = load()
+    info = (C.c_uint32 * 4)()
+    check(lib.rt_debug_iow_dump(handle, info, None, None), "rt_debug_iow_dump")
+    if not info[0]:
+        return None
+    n = iow_info(handle)["objects"]
+    wide = np.zeros((info[0], 32), np.float32)
+    raw = np.zeros(6 * n, np.float32)
+    check(lib.rt_debug_iow_dump(handle, info, fptr(wide), fptr(raw)), "rt_debug_iow_dump")
     obox = np.concatenate([raw[:4 * n].reshape(n, 4), raw[4 * n:].reshape(n, 2)], axis=1)
     return {"wide": wide, "obox": obox}
 
