@@ -172,6 +172,9 @@ typedef struct rt_options {
     int spec_solo;          /* re-run pass: the longest samples take a wave each, up to this many */
     int spec_validate;      /* the sequential leftover pass reuses still-exact records */
     double spec_max_gb;     /* device memory cap of the speculation records, GB */
+    int inw_sky_blocks;     /* INW-01, 1 (default): pixel-major frames render the 8x8 blocks whose pixels have empty,
+                               complete beam lists (no primary ray can reach an object) in the lean kernel
+                               k_inw_sky, outside k_inw_pm's claims (DESIGN.md §5.1 "Sky blocks") */
 } rt_options;
 void rt_options_default(rt_options *o);
 int  rt_options_set(const rt_options *o);   /* RT_E_ARG: null, wrong size or a value out of range */

@@ -39,6 +39,12 @@ typedef struct rt_path_info {
     int sphere_records;   /* INW: 1 when the object tests read the sphere records (inw_sphere_records) */
 } rt_path_info;
 int rt_debug_path(rt_dev_scene *s, rt_path_info *out);
+/* Sky blocks of the scene's last INW fold render (rt_options.inw_sky_blocks; synchronises): out[0] =
+ * 8x8 blocks the classifier flagged (every pixel's beam lists empty and complete), out[1] = those of
+ * them k_inw_sky rendered (the others held a ray that fails the beam lists' test and went back to
+ * k_inw_pm), out[2] = the frame's blocks.  A frame the path does not apply to reports 0 flagged.
+ * s == NULL: the same of the last blocking render (rt_render_inw and its kin build a scene per call). */
+int rt_debug_sky_blocks(rt_dev_scene *s, uint32_t out[3]);
 
 /* ---- diagnostics ---------------------------------------------------------------------
  * d_buf: device array of 16 uint64 (or NULL to disable).  While set, the IOW-03 kernel adds

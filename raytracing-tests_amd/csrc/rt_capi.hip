@@ -33,6 +33,7 @@ rt_options default_options() {
     o.spec_tail_budget = 3072; o.spec_scan = 128; o.spec_chain = 1; o.spec_alt = 1; o.spec_alt_cap = 1 << 17;
     o.spec_alt_seg = 0; o.spec_alt_every = 0; o.spec_spread = 1; o.spec_prior_from = 2; o.spec_sort = 1;
     o.spec_solo = 4096; o.spec_validate = 1; o.spec_max_gb = 96.0;
+    o.inw_sky_blocks = 1;
     return o;
 }
 bool options_ok(const rt_options *o) {

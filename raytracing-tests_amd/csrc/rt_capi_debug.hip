@@ -10,6 +10,7 @@
 unsigned long long *g_dbg = nullptr;
 unsigned *g_px_rays = nullptr;
 bool g_time_kernels = false;
+uint32_t g_sky_blocking[3] = {0, 0, 0};
 
 namespace {
 
@@ -201,6 +202,14 @@ int rt_debug_launches(rt_dev_scene *s, char *name_out, int name_cap) {
     return L.launches;
 }
 
+int rt_debug_sky_blocks(rt_dev_scene *s, uint32_t out[3]) {
+    if (!out) return RT_E_ARG;
+    if (!s) {  // the last blocking render (its scene is gone)
+        std::memcpy(out, g_sky_blocking, sizeof(g_sky_blocking));
+        return RT_OK;
+    }
+    return sky_blocks_of(s, out);
+}
 int rt_debug_chunks(rt_dev_scene *s) {
     if (!s) return RT_E_ARG;
     return s->last.chunks;

@@ -20,6 +20,7 @@ extern unsigned long long *g_dbg;      // rt_debug_counters(): lane-occupancy di
 extern unsigned *g_px_rays;            // rt_debug_pixel_rays(): rays per work unit
 extern int g_build_levels;             // rt_debug_build_level_cap(): the device build's level cap (0 = 256)
 extern bool g_time_kernels;            // rt_debug_time_kernels
+extern uint32_t g_sky_blocking[3];     // rt_debug_sky_blocks(NULL): the last blocking render's sky blocks
 
 // IOW-03: the culling BVH beside the shared node buffer, and the RI values of its materials
 struct IowCullPriors {
@@ -131,6 +132,8 @@ struct LastRender {
     bool lring_sm = false;     // ... k_inw_sm's
     bool gq = false;           // ... k_inw_pm's GQ instance (quantised nodes, global stacks)
     uint32_t ring[2] = {0, 0}; // ... its fold windows (pixel-major, sample-major)
+    bool sky = false;          // ... it ran the sky-block kernels (rt_debug_sky_blocks)
+    uint32_t sky_blocks = 0;   // ... the frame's 8x8 blocks
 };
 
 // A prepared scene: device-resident records, LBVH nodes, lights and sample tables.
@@ -280,6 +283,8 @@ rtk::Frame make_frame(const rt_camera *cam, const rt_params *p);
 int ensure_workspace(rt_dev_scene *s, uint32_t units);
 int ensure_cont(rt_dev_scene *s);
 int launch_scene(rt_dev_scene *s, rtk::Frame &f, hipStream_t st);
+// rt_debug_sky_blocks of a scene's last render (synchronises when the sky-block kernels ran)
+int sky_blocks_of(rt_dev_scene *s, uint32_t out[3]);
 int render_blocking(rt_dev_scene *s, const rt_camera *cam, const rt_params *p, float *rgba, float *depth,
                     rt_stats *st);
 // rt_launch_spec.hip

@@ -38,15 +38,26 @@ __device__ __forceinline__ f3 inw_pixel_dir(const Frame &F, int px, int py) {
     f3 cr = cross(D, up), cu = cross(cr, D);
     return normalize((D * F.screen_dist + cr * srx) + cu * sry);
 }
-// cd: the pixel's direction (inw_pixel_dir), which callers that keep it per pixel pass in
-template <class KS>
-__device__ __forceinline__ void inw_start_sample_cd(const InwScene &S, const Frame &F, KS &K, f3 cd, int s, Ctr &c) {
-    K.reset(0);
+// The single-focus camera ray of sample s (01_BVH...glsl:402-410): from the lens point, one unit
+// behind the tip, at the focal point.  Shared by the sample start below and k_inw_sky.
+__device__ __forceinline__ void inw_camera_ray(const InwScene &S, const Frame &F, f3 cd, int s, f3 &o, f3 &d) {
     const f3 up = f3{0, 1, 0};
     f3 co = mk(F.pos[0], F.pos[1], F.pos[2]);
     float ox = S.sunflower[2 * s] * (F.aperture * 0.5f), oy = S.sunflower[2 * s + 1] * (F.aperture * 0.5f);
     f3 rr = cross(cd, up), ru = cross(rr, cd);
+    f3 tip = ((co + cd) + rr * ox) + ru * oy;
+    d = normalize((co + cd * F.focus) - tip);
+    o = tip - d;
+}
+// cd: the pixel's direction (inw_pixel_dir), which callers that keep it per pixel pass in
+template <class KS>
+__device__ __forceinline__ void inw_start_sample_cd(const InwScene &S, const Frame &F, KS &K, f3 cd, int s, Ctr &c) {
+    K.reset(0);
     if (F.n_focus > 0) {  // MULTIFOCUS lens record (01_BVH...glsl:388-400): stack floats 0..5
+        const f3 up = f3{0, 1, 0};
+        f3 co = mk(F.pos[0], F.pos[1], F.pos[2]);
+        float ox = S.sunflower[2 * s] * (F.aperture * 0.5f), oy = S.sunflower[2 * s + 1] * (F.aperture * 0.5f);
+        f3 rr = cross(cd, up), ru = cross(rr, cd);
         const float first_limit = F.focus_list[0] * 0.5f;
         const f3 nd = normalize((cd * first_limit + rr * ox) + ru * oy);
         const f3 rn = normalize((-rr) * ox - ru * oy);
@@ -56,9 +67,9 @@ __device__ __forceinline__ void inw_start_sample_cd(const InwScene &S, const Fra
         K.push_ray(co, nd, 1.0f, 0.0f, c);
         return;
     }
-    f3 tip = ((co + cd) + rr * ox) + ru * oy;
-    f3 la = normalize((co + cd * F.focus) - tip);
-    K.push_ray(tip - la, la, 1.0f, 0.0f, c);
+    f3 o, la;
+    inw_camera_ray(S, F, cd, s, o, la);
+    K.push_ray(o, la, 1.0f, 0.0f, c);
 }
 template <class KS>
 __device__ __forceinline__ void inw_start_sample(const InwScene &S, const Frame &F, KS &K, int px, int py, int s,

@@ -1443,6 +1443,116 @@ __global__ __launch_bounds__(kBlock) void k_inw_probe(Frame f, InwScene S, uint3
     }
 }
 
+// Sky blocks (DESIGN.md §5.1 "Sky blocks"; rt_options.inw_sky_blocks).  An 8x8 block whose 64 units
+// have an empty and complete beam list in every time bin (count 0, cut kMiss, not kBeamOff) holds
+// no pixel whose primary rays can reach a culling box: inw_closest_beam answers "no hit" for every
+// such ray that passes its `ok` test, and the sample is the miss branch of inw_segment.  k_inw_sky
+// renders those blocks without stacks, walk or ring; the claim-order kernels put them first and
+// k_inw_pm's queues start past them.  A block with a ray that fails the test is left to k_inw_pm (its flag cleared).
+// Bookkeeping: kSkyInfo uints after the claim order's 256 buckets.
+enum { kSkySkip = 0,     // blocks at the head of the claim order that k_inw_pm skips (k_inw_order_scan)
+       kSkyFlagged = 1,  // blocks the classifier flagged
+       kSkyDone = 2,     // ... of them, those k_inw_sky rendered
+       kSkyHead = 3,     // k_inw_order_scatter: cursor of the sky blocks at the head of the order
+       kSkyInfo = 16 };
+// one wave per 8x8 block; on a sample-major frame every flag is cleared
+__global__ __launch_bounds__(kBlock) void k_inw_sky_classify(Frame f, InwScene S, uint32_t *flag, uint32_t *info,
+                                                             const uint32_t *mode, uint32_t force) {
+    const uint32_t lane = threadIdx.x & 63u, nblk = units_total(f) / 64u;
+    const uint32_t blk = (blockIdx.x * kBlock + threadIdx.x) >> 6;
+    if (blk >= nblk) return;  // whole waves
+    bool empty = !inw_sample_major(mode, force);
+    const uint32_t nb = S.beam_bins > 1u ? S.beam_bins : 1u, u = blk * 64u + lane;
+    for (uint32_t b = 0; b < nb && empty; b++) {  // padding units have empty lists too (k_inw_beam)
+        const uint32_t nw = S.beam_n[b * S.beam_units + u];
+        empty = nw != kBeamOff && (nw & 0xffu) == 0u && S.beam_cut[b * S.beam_units + u] == kMiss;
+    }
+    const bool sky = __ballot(!empty) == 0ull;
+    if (lane == 0) {
+        flag[blk] = sky ? 1u : 0u;
+        if (sky) atomicAdd(info + kSkyFlagged, 1u);
+    }
+}
+// One 512-lane block per flagged 8x8 block, a wave per row of 8 pixels.  A pass takes 8 samples of
+// each pixel (lane = sample * 8 + pixel): the camera ray, the `ok` test, background(cd) and the
+// three square roots, staged in LDS; then lane (channel * 8 + pixel) adds its pixel's 8 values in
+// sample order -- End()'s sum, one chain per pixel and channel, 24 chains abreast.
+// The test is inw_closest_beam's `ok` for a fresh sample, from below: a direction component of
+// magnitude >= 2^-100 is non-zero with a finite correctly rounded reciprocal, so no reciprocal is
+// computed (a smaller or NaN component sends the block to k_inw_pm, which is always exact).
+constexpr int kSkyBlock = 512, kSkyPlane = 72;  // a channel's 64 staged values, padded: the three planes on distinct banks
+__global__ __launch_bounds__(kSkyBlock) __attribute__((amdgpu_waves_per_eu(8))) void k_inw_sky(Frame f, InwScene S, uint32_t *flag, uint32_t *info) {
+    const uint32_t blk = blockIdx.x;
+    if (!uni(flag[blk])) return;  // the whole block
+    __shared__ float s_sq[(kSkyBlock / 64) * 3 * kSkyPlane];
+    __shared__ uint32_t s_bad;
+    if (threadIdx.x == 0) s_bad = 0u;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, row = threadIdx.x >> 6, p = lane & 7u, k = lane >> 3;
+    float *sq = s_sq + row * (3 * kSkyPlane);
+    const UnitPix px = unit_pixel(f, blk * 64u + row * 8u + p);
+    const f3 pcd = px.in_image ? inw_pixel_dir(f, px.x, px.y) : f3{0, 0, 0};
+    // the fold's lanes: pixel fp of the row, channel fc
+    const uint32_t fp = lane & 7u, fc = lane >> 3;
+    const bool folds = fc < 3u && __shfl((int)px.in_image, (int)fp, 64) != 0;
+    const uint32_t spp = (uint32_t)f.spp;
+    float acc = 0.0f;
+    bool bad = false;
+    for (uint32_t s0 = 0; s0 < spp; s0 += 8u) {
+        const uint32_t s = s0 + k;
+        if (px.in_image && s < spp) {
+            f3 o, d;
+            inw_camera_ray(S, f, pcd, (int)s, o, d);
+            bad = bad || !(__builtin_fabsf(d.x) >= 0x1p-100f && __builtin_fabsf(d.y) >= 0x1p-100f &&
+                           __builtin_fabsf(d.z) >= 0x1p-100f);
+            const f3 col = f3{0, 0, 0} + background(d, false) * 1.0f;  // inw_segment's miss branch
+            sq[lane] = __builtin_sqrtf(col.x);
+            sq[kSkyPlane + lane] = __builtin_sqrtf(col.y);
+            sq[2 * kSkyPlane + lane] = __builtin_sqrtf(col.z);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (folds) {
+            const uint32_t n = spp - s0 < 8u ? spp - s0 : 8u;
+            const float *v = sq + fc * kSkyPlane + fp;
+            uint32_t j = 0;
+            if (s0 == 0) { acc = v[0]; j = 1; }
+            if (n == 8u) {
+                float a[8];
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; q++) a[q] = v[q * 8u];
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; q++)
+                    if (q >= j) acc = acc + a[q];
+            } else {
+                for (; j < n; j++) acc = acc + v[j * 8u];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (__ballot(bad) != 0ull && lane == 0) atomicOr(&s_bad, 1u);
+    __syncthreads();
+    if (s_bad) {  // some ray fails the test: nothing written, k_inw_pm renders the block
+        if (threadIdx.x == 0) flag[blk] = 0u;
+        return;
+    }
+    // the row's stores: 8 lanes, 128 B of colour and 32 B of depth (End()'s imageStores, 01_BVH...glsl:652, 667-668)
+    const float inv = rcp((float)f.spp);
+    const float ax = __shfl(acc, (int)p, 64), ay = __shfl(acc, (int)(8u + p), 64), az = __shfl(acc, (int)(16u + p), 64);
+    if (k == 0 && px.out != (size_t)-1) {
+        fb_store(f, px.out, make_float4(px.in_image ? ax * inv : 0.0f, px.in_image ? ay * inv : 0.0f,
+                                        px.in_image ? az * inv : 0.0f, px.in_image ? 1.0f : 0.0f));
+        if (f.out_depth) depth_store(f, px.out, px.in_image ? kMaxT : 0.0f);  // the middle sample's depth: a miss
+    }
+    // one segment per sample; no node, test, shadow ray, drop or NaN
+    const unsigned long long rays = (unsigned long long)__popcll(__ballot(k == 0 && px.in_image)) * spp;
+    if (lane == 0 && rays && f.counters) atomicAdd(f.counters, rays);
+    if (threadIdx.x == 0) atomicAdd(info + kSkyDone, 1u);
+}
+
 // Claim order (DESIGN.md §5 "Claim order"): a persistent fold kernel's tail is the last pixels
 // it claims -- a wave needs spp / 64 rounds of samples for one pixel, so expensive pixels claimed
 // last leave the rest of the chip idle.  k_inw_cost estimates each pixel's cost from the primary
@@ -1454,9 +1564,11 @@ __global__ __launch_bounds__(kBlock) void k_inw_probe(Frame f, InwScene S, uint3
 // which wave traces which pixel when: every pixel's samples and sums are the same.  Pixel-major
 // frames only: the three kernels exit at once when the probe picked k_inw_sm, whose 8x8 blocks
 // keep their spatial order (measured: C5 3% slower with it, the blocks' locality lost).
+// flag (null: none): the sky blocks k_inw_sky rendered (below); they get no bucket, key kSkyKey
+constexpr uint32_t kSkyKey = 0xffffffffu;
 template <bool LIGHTS>
 __global__ __launch_bounds__(kBlock) void k_inw_cost(Frame f, InwScene S, uint32_t *key, uint32_t *hist,
-                                                     const uint32_t *mode, uint32_t force) {
+                                                     const uint32_t *mode, uint32_t force, const uint32_t *flag) {
     if (inw_sample_major(mode, force)) return;
     __shared__ float lds[kFStack * kBlock];
     Ctr c;  // not flushed: these rays are not the frame's
@@ -1466,6 +1578,10 @@ __global__ __launch_bounds__(kBlock) void k_inw_cost(Frame f, InwScene S, uint32
     const uint32_t lane = threadIdx.x & 63u, nblk = units_total(f) / 64u, p = lane;
     const uint32_t blk = ((blockIdx.x * kBlock + threadIdx.x) >> 6);
     float est = 0.0f;
+    if (blk < nblk && flag && uni(flag[blk])) {  // (wave-uniform: blk is per wave)
+        if (p == 0) key[blk] = kSkyKey;
+        return;
+    }
     if (blk < nblk) {
         const UnitPix px = unit_pixel(f, blk * 64u + p);
         for (int si = 0; si < 2 && px.in_image; si++) {
@@ -1501,8 +1617,10 @@ __global__ __launch_bounds__(kBlock) void k_inw_cost(Frame f, InwScene S, uint32
         atomicAdd(hist + (255u - k), 1u);
     }
 }
-// exclusive scan of the 256 bucket counts (one 256-lane block)
-__global__ __launch_bounds__(256) void k_inw_order_scan(uint32_t *hist, const uint32_t *mode, uint32_t force) {
+// exclusive scan of the 256 bucket counts (one 256-lane block).  The blocks without a bucket -- the
+// sky blocks, nblk less the buckets' sum -- lead the order, so the buckets' offsets start past them;
+// hist[256 + kSkySkip] = their count
+__global__ __launch_bounds__(256) void k_inw_order_scan(uint32_t *hist, uint32_t nblk, const uint32_t *mode, uint32_t force) {
     if (inw_sample_major(mode, force)) return;
     __shared__ uint32_t t[256];
     const uint32_t i = threadIdx.x;
@@ -1515,14 +1633,25 @@ __global__ __launch_bounds__(256) void k_inw_order_scan(uint32_t *hist, const ui
         t[i] += a;
         __syncthreads();
     }
-    hist[i] = t[i] - v;
+    const uint32_t skip = nblk - t[255];
+    hist[i] = skip + t[i] - v;
+    if (i == 0u) hist[256u + kSkySkip] = skip;
 }
 __global__ __launch_bounds__(kBlock) void k_inw_order_scatter(const uint32_t *key, uint32_t *off, uint32_t *order,
                                                                uint32_t nblk, const uint32_t *mode, uint32_t force) {
     if (inw_sample_major(mode, force)) return;
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nblk) return;
-    order[atomicAdd(off + (255u - key[i]), 1u)] = i;
+    const uint32_t k = key[i];
+    order[atomicAdd(k == kSkyKey ? off + 256u + kSkyHead : off + (255u - k), 1u)] = i;
+}
+// k_inw_pm claims through the order from its queues' counters on: they start past the sky blocks
+// (counter[0]: the one queue, in units; counter[64 + 16 x]: queue x of the per-XCD queues, which
+// holds the claim ordinals congruent to x mod 8), so k_inw_pm itself knows nothing of them
+__global__ __launch_bounds__(64) void k_inw_sky_queues(const uint32_t *info, unsigned *counter) {
+    const uint32_t x = threadIdx.x, skip = info[kSkySkip];
+    if (x == 0u) counter[0] = skip * 64u;
+    if (x < 8u) counter[64u + 16u * x] = skip > x ? ((skip - x + 7u) >> 3) * 64u : 0u;
 }
 
 // pixel-major stream (see above): entry g = (claimed pixel ordinal j, sample s).  LN: 768-lane
@@ -2341,12 +2470,18 @@ hipError_t launch_inw_beam(const Frame &f, const InwScene &sc, const uint32_t *m
     hipLaunchKernelGGL(k_inw_beam, dim3((n + kBeamBlock - 1) / kBeamBlock, nb), dim3(kBeamBlock), 0, s, f, sc, mode, force);
     return hipGetLastError();
 }
+size_t inw_cost_uints(uint32_t nblk) { return 3 * size_t(nblk) + 256 + kSkyInfo; }
+size_t inw_sky_info_at(uint32_t nblk) { return 2 * size_t(nblk) + 256; }
 // One frame of the on-chip-fold INW kernels: the probe (unless forced), then k_inw_pm and
 // k_inw_sm, of which the one the probe did not pick exits at once.  ring: blocks * 4 waves *
 // max(ring_pm, ring_sm) float4; mode: 2 uints (zeroed here).  force: 0 = probe, 1 = pm, 2 = sm.
+// sky (needs cost and sc.beam): the sky blocks rendered by k_inw_sky -- the beam lists, the
+// classifier and k_inw_sky then come before the claim-order kernels, which put the blocks whose flag
+// k_inw_sky left standing at the head of the order, and k_inw_sky_queues starts k_inw_pm's queues
+// past them.
 hipError_t launch_inw_fold(const Frame &f, const InwScene &sc, float4 *ring, uint32_t ring_pm, uint32_t ring_sm,
                            unsigned *counter, uint32_t *mode, uint32_t force, int blocks, int blocks_ln,
-                           uint32_t *cost, hipStream_t s) {
+                           uint32_t *cost, bool sky, hipStream_t s) {
     for (uint32_t r : {ring_pm, ring_sm})
         if (r < 64 || (r & (r - 1))) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(mode, 0, 2 * sizeof(uint32_t), s);
@@ -2361,26 +2496,36 @@ hipError_t launch_inw_fold(const Frame &f, const InwScene &sc, float4 *ring, uin
         else hipLaunchKernelGGL(k_inw_probe<false>, g, dim3(kBlock), 0, s, f, sc, stride, mode);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    // claim order of k_inw_pm (cost: 2 * nblk + 256 uints, or null = unit order)
+    // claim order of k_inw_pm (cost: 3 * nblk + 256 + kSkyInfo uints -- keys, the order, buckets, the
+    // sky blocks' bookkeeping and flags -- or null = unit order)
     const uint32_t *border = nullptr;
-    if (cost && units_of(f) >= 64u) {
+    const bool order = cost && units_of(f) >= 64u;
+    sky = sky && order && sc.beam;
+    if (order) {
         const uint32_t nblk = units_of(f) / 64u;
-        uint32_t *key = cost, *order = cost + nblk, *hist = cost + 2 * nblk;
-        if ((e = hipMemsetAsync(hist, 0, 256 * sizeof(uint32_t), s)) != hipSuccess) return e;
+        uint32_t *key = cost, *ord = cost + nblk, *hist = cost + 2 * nblk, *flag = hist + 256 + kSkyInfo;
+        if ((e = hipMemsetAsync(hist, 0, (256 + kSkyInfo) * sizeof(uint32_t), s)) != hipSuccess) return e;
         const dim3 g((nblk + 3u) / 4u);  // 4 blocks of 8x8 pixels per 256-lane block
-        if (sc.layout == 4) hipLaunchKernelGGL(k_inw_cost<true>, g, dim3(kBlock), 0, s, f, sc, key, hist, mode, force);
-        else hipLaunchKernelGGL(k_inw_cost<false>, g, dim3(kBlock), 0, s, f, sc, key, hist, mode, force);
-        hipLaunchKernelGGL(k_inw_order_scan, dim3(1), dim3(256), 0, s, hist, mode, force);
+        if (sky) {
+            if ((e = launch_inw_beam(f, sc, mode, force, s)) != hipSuccess) return e;
+            hipLaunchKernelGGL(k_inw_sky_classify, g, dim3(kBlock), 0, s, f, sc, flag, hist + 256, mode, force);
+            hipLaunchKernelGGL(k_inw_sky, dim3(nblk), dim3(kSkyBlock), 0, s, f, sc, flag, hist + 256);
+        }
+        const uint32_t *fl = sky ? flag : nullptr;
+        if (sc.layout == 4) hipLaunchKernelGGL(k_inw_cost<true>, g, dim3(kBlock), 0, s, f, sc, key, hist, mode, force, fl);
+        else hipLaunchKernelGGL(k_inw_cost<false>, g, dim3(kBlock), 0, s, f, sc, key, hist, mode, force, fl);
+        hipLaunchKernelGGL(k_inw_order_scan, dim3(1), dim3(256), 0, s, hist, nblk, mode, force);
         hipLaunchKernelGGL(k_inw_order_scatter, dim3((nblk + kBlock - 1) / kBlock), dim3(kBlock), 0, s, key, hist,
-                           order, nblk, mode, force);
+                           ord, nblk, mode, force);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        border = order;
+        border = ord;
     }
-    if (sc.beam && (e = launch_inw_beam(f, sc, mode, force, s)) != hipSuccess) return e;
+    if (sc.beam && !sky && (e = launch_inw_beam(f, sc, mode, force, s)) != hipSuccess) return e;
     for (int k = 0; k < 2; k++) {  // (pm, then sm) each with its own queue counter
         if ((e = hipMemsetAsync(counter + 16 * k, 0, sizeof(unsigned), s)) != hipSuccess) return e;
         if (k == 0 && sc.xcdq && (e = hipMemsetAsync(counter + 64, 0, 8 * 16 * sizeof(unsigned), s)) != hipSuccess)
             return e;  // k_inw_pm's per-XCD queues
+        if (k == 0 && sky) hipLaunchKernelGGL(k_inw_sky_queues, dim3(1), dim3(64), 0, s, cost + inw_sky_info_at(units_of(f) / 64u), counter);
         const uint32_t rm = (k == 0 ? ring_pm : ring_sm) - 1u;
         unsigned *ctr = counter + 16 * k;
         if (blocks_ln > 0) {  // the LDS-staged BVH top (768-lane blocks); FU: the fused-fma cull

@@ -214,11 +214,17 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     // claim order, costliest blocks first (inw_claim_order = 0: unit order)
     uint32_t *cost = nullptr;
     if (o.inw_claim_order) {
-        const size_t need = (2 * size_t(rtk::units_of(f) / 64) + 256) * sizeof(uint32_t);
+        const size_t need = rtk::inw_cost_uints(rtk::units_of(f) / 64) * sizeof(uint32_t);
         if (fold.cost.reserve(need) != hipSuccess) return RT_E_HIP;
         cost = fold.cost.as<uint32_t>();
     }
     if (int rc = set_beam(s, f, sc); rc != RT_OK) return rc;
+    // sky blocks (inw_sky_blocks = 0: off): INW-01 frames with beam lists and the claim
+    // order, the single-focus camera, a fresh sample's stack below the wide walk's condition, no
+    // per-pixel ray count or occupancy hook; the pixel-major verdict is read on the device
+    const bool sky = o.inw_sky_blocks && s->layout != 4 && s->n_lights == 0 && f.n_focus == 0 && sc.beam && cost &&
+                     rtk::units_of(f) >= 64u && force != 2 && 8u + w.dfs_high <= uint32_t(rtk::kFStack) &&
+                     !f.px_rays && !f.dbg;
     {  // what this frame runs (the fold order, and with it the kernel's name, is resolved at query time)
         LastRender last;
         std::snprintf(last.kernel, sizeof(last.kernel), "%s", s->layout == 4 ? "k_inw_fold<true>" : "k_inw_fold<false>");
@@ -233,6 +239,8 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
         last.lring_sm = lring_sm;
         last.ln = blocks_ln > 0;
         last.fu = last.ln && sc.fused;
+        last.sky = sky;
+        last.sky_blocks = rtk::units_of(f) / 64;
         rt_path_info &P = last.path;
         P.launches = 1;
         P.order_forced = force != 0;
@@ -261,7 +269,7 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     if (e == hipSuccess && ev) e = hipEventRecord(ev->first, st);
     if (e == hipSuccess)
         e = rtk::launch_inw_fold(f, sc, fold.ring.as<float4>(), ring_pm, ring_sm, s->counter.as<unsigned>(),
-                                 fold.mode.as<uint32_t>(), force, blocks, blocks_ln, cost, st);
+                                 fold.mode.as<uint32_t>(), force, blocks, blocks_ln, cost, sky, st);
     if (e == hipSuccess && ev) e = hipEventRecord(ev->second, st);
     if (e != hipSuccess) {
         fold.ring_frame = 0;
@@ -347,6 +355,21 @@ int launch_scene(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     return e == hipSuccess ? RT_OK : launch_failed(e);
 }
 
+// rt_debug_sky_blocks of the scene's last render: (flagged, rendered by k_inw_sky, blocks of the frame)
+int sky_blocks_of(rt_dev_scene *s, uint32_t out[3]) {
+    const LastRender &L = s->last;
+    out[0] = out[1] = 0;
+    out[2] = L.sky_blocks;
+    if (!L.sky) return RT_OK;
+    uint32_t info[3] = {0, 0, 0};  // (blocks k_inw_pm skips, flagged, rendered)
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(info, s->fold.cost.as<uint32_t>() + rtk::inw_sky_info_at(L.sky_blocks), sizeof(info),
+                     hipMemcpyDeviceToHost));
+    out[0] = info[1];
+    out[1] = info[2];
+    return RT_OK;
+}
+
 // blocking render of one scene into host buffers
 int render_blocking(rt_dev_scene *s, const rt_camera *cam, const rt_params *p, float *rgba, float *depth,
                     rt_stats *st) {
@@ -368,6 +391,7 @@ int render_blocking(rt_dev_scene *s, const rt_camera *cam, const rt_params *p, f
     const int rc = timed([&] { return launch_scene(s, f, nullptr); }, &ms);
     if (rc != RT_OK) return rc;
     HIP_OK(hipDeviceSynchronize());
+    if (int rs = sky_blocks_of(s, g_sky_blocking); rs != RT_OK) return rs;
     HIP_OK(hipMemcpy(rgba, d_rgba.p, npx * 16, hipMemcpyDeviceToHost));
     if (depth) HIP_OK(hipMemcpy(depth, d_depth.p, npx * 4, hipMemcpyDeviceToHost));
     return st ? read_stats(d_ctr.p, ms, st) : RT_OK;

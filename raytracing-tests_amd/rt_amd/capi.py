@@ -80,7 +80,7 @@ class RtOptions(C.Structure):
         "rounds_seq", "rounds_spec", "park_min",
         "spec_iters", "spec_probe", "spec_heavy", "spec_rounds", "spec_tail_rounds", "spec_tail_budget", "spec_scan",
         "spec_chain", "spec_alt", "spec_alt_cap", "spec_alt_seg", "spec_alt_every", "spec_spread", "spec_prior_from",
-        "spec_sort", "spec_solo", "spec_validate")] + [("spec_max_gb", C.c_double)]
+        "spec_sort", "spec_solo", "spec_validate")] + [("spec_max_gb", C.c_double), ("inw_sky_blocks", C.c_int)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
@@ -186,6 +186,7 @@ SIGNATURES = {
     "rt_debug_iow_info": (C.c_int, [C.c_void_p, _U32P]),
     "rt_debug_iow_dump": (C.c_int, [C.c_void_p, _U32P, _FP, _FP]),
     "rt_debug_path": (C.c_int, [C.c_void_p, C.POINTER(RtPathInfo)]),
+    "rt_debug_sky_blocks": (C.c_int, [C.c_void_p, _U32P]),
     "rt_debug_wide_info": (C.c_int, [C.c_void_p, _U32P, _U32P]),
     "rt_tile_deal": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _IP, C.c_int]),
     "rt_group_create": (C.c_void_p, [_IP, C.c_int]),
@@ -318,6 +319,14 @@ def debug_path(scene_handle) -> dict:
     p = RtPathInfo()
     check(load().rt_debug_path(scene_handle, C.byref(p)), "rt_debug_path")
     return p.as_dict()
+
+
+def debug_sky_blocks(scene_handle) -> tuple:
+    """rt_debug_sky_blocks of a device scene's last render: (blocks flagged, of them rendered by
+    k_inw_sky, blocks of the frame)."""
+    out = (C.c_uint32 * 3)()
+    check(load().rt_debug_sky_blocks(scene_handle, out), "rt_debug_sky_blocks")
+    return tuple(out)
 
 
 # ----------------------------------------------------------------------------- scenes
