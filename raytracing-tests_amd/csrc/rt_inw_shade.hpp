@@ -1,7 +1,7 @@
 // rt_inw_shade.hpp -- one iteration of the INW shaders' ray loop as a device function
 // (inw_segment: pop a ray, closest hit, material and texture, surrounding RI, INW-04's shadow rays,
 // the scatter step and its pushes on the 40-float stack), with the sample start of out_Pixel's
-// prologue and the helpers they use.  Included by rt_kernels.hip (the render kernels) and
+// prologue and the helpers they use.  Included by rt_inw_render.hip and rt_inw_fold.hip (the render kernels) and
 // rt_paths.hip (the path-query kernel), so a frame and a path query run the same segment.
 #pragma once
 #include "rt_kernels.hpp"

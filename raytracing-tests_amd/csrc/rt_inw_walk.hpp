@@ -1,8 +1,8 @@
 // rt_inw_walk.hpp -- the INW closest-hit and surrounding-RI walks as device functions: the
 // reference's LBVH walks (01_BVH...glsl:431-473, 486-502) on the 40-float stack, the stackless
 // forms, the 4-wide culling walk with its node fetches and object tests, the beam-list and RI-grid
-// queries, and inw_closest / inw_ri, which pick among them.  Included by rt_kernels.hip (the render
-// kernels) and rt_trace.hip (the ray-query kernel), so both run the same walk.
+// queries, and inw_closest / inw_ri, which pick among them.  Included by rt_inw_render.hip and
+// rt_inw_fold.hip (the render kernels) and rt_trace.hip (the ray-query kernel), so both run the same walk.
 #pragma once
 #include "rt_kernels.hpp"
 #include "rt_math.hpp"

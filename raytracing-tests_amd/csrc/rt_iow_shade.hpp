@@ -1,7 +1,7 @@
 // rt_iow_shade.hpp -- one ray segment of the IOW-03 sample loop as device functions: the scatter
 // direction, the 4-entry ray stack, and pop / closest hit / shade / push (LaunchRays,
-// 03_Shadows_and_Materials/computeShaderSrc.glsl:258-358).  Included by rt_kernels.hip (the render
-// kernels) and rt_path_iow.hip (the path-query kernel), so both run the same segment.
+// 03_Shadows_and_Materials/computeShaderSrc.glsl:258-358).  Included by rt_iow_coop.hpp (the render
+// kernels of rt_iow_render.hip and rt_iow_spec.hip) and rt_path_iow.hip (the path-query kernel), so both run the same segment.
 #pragma once
 #include "rt_iow_walk.hpp"
 
@@ -152,7 +152,7 @@ __device__ __forceinline__ void iow_camera_ray(const IowScene &S, const Frame &f
     rd = normalize((ld * f.screen_dist + r_ * (sx + dsx * (float)ix)) + u_ * (sy + dsy * (float)iy));
 }
 // The four scalars it takes, as out_Pixel forms them (03...glsl:370-380): the pixel's screen position
-// (sx, sy) and the sub-pixel steps (dsx, dsy).  The render kernels (rt_kernels.hip) and k_camera_rays
+// (sx, sy) and the sub-pixel steps (dsx, dsy).  The render kernels (rt_iow_render.hip, rt_iow_spec.hip) and k_camera_rays
 // (rt_pixels.hip) call these.
 // The ring schedule's grid and the aspect ratio under them: k_camera_rays calls these two; the render
 // kernels keep the same two statements inline (calling them here changed their device code's bytes,

@@ -1,7 +1,7 @@
 // rt_iow_walk.hpp -- the IOW-03 closest-hit search as device functions: the object records and
 // their exact tests, the 4-wide culling walk with postponed leaves (nodes in LDS or global memory),
 // the reference's linear loop, and the hit evaluation (LaunchRay, 03...glsl:196-256).  Included by
-// rt_kernels.hip (the render kernels) and rt_trace_iow.hip (the ray-query kernel), so both run the
+// rt_iow_render.hip and rt_iow_spec.hip (the render kernels) and rt_trace_iow.hip (the ray-query kernel), so both run the
 // same search.
 #pragma once
 #include "rt_kernels.hpp"

@@ -1,4 +1,6 @@
-// rt_kernels.hpp -- launch-side declarations shared by rt_kernels.hip and rt_capi.hip.
+// rt_kernels.hpp -- launch-side declarations shared by the kernel units (rt_iow_render.hip,
+// rt_iow_spec.hip, rt_inw_render.hip, rt_inw_fold.hip, rt_diag_kernels.hip and the query, build and
+// stage units) and the host units that launch them (rt_scene_build.hip, rt_launch*.hip, rt_capi*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -107,7 +109,7 @@ struct InwScene {
     uint32_t lring = 0;       // k_inw_pm (768-lane instances): the fold ring in LDS (kPmLdsRing entries per wave)
     uint32_t lring_sm = 0;    // k_inw_sm (768-lane instances): the same
     uint32_t xcdq = 0;        // k_inw_pm claims from per-XCD queues (rt_options.inw_claim_xcd)
-    uint32_t ring_epoch = 0;  // fold-ring tags: the frame's epoch (0..62) << 26 (ring_tag, rt_kernels.hip)
+    uint32_t ring_epoch = 0;  // fold-ring tags: the frame's epoch (0..62) << 26 (ring_tag, rt_inw_fold.hip)
     // Quantised wide nodes (DESIGN.md §5.2 "Quantised nodes"; null = off): the culling BVH of
     // wnodes as 4 float4 per node -- origin.xyz, scale.x | scale.yz, low-plane bytes x, y | low z,
     // high x, y, z (byte k = child k) | links -- each plane rounded outward (rt_build.hip:
@@ -245,7 +247,7 @@ enum { kSpecFirst = 0, kSpecRest = 1, kSpecList = 2 };
 // lanes from `in` in full waves.  in == null: the launch's units are pixels.  out == null or
 // fewer than park_min units in the launch: lanes run to completion (the final round).
 constexpr int kBlock = 256;      // threads per block of every render kernel
-constexpr int kInwLdsNodes = 236;        // wide BVH nodes the INW fold kernels stage in LDS (rt_kernels.hip)
+constexpr int kInwLdsNodes = 236;        // wide BVH nodes the INW fold kernels stage in LDS (rt_inw_fold.hip)
 constexpr uint32_t kPmLdsRing = 256;     // k_inw_pm's LDS fold ring: entries per wave (InwScene::lring) ...
 constexpr uint32_t kPmLdsNodes = 5;      // ... and the nodes it leaves staged
 // k_inw_pm's GQ instance (DESIGN.md §5.1 "GQ": the reference's 40-float stacks in global memory):
@@ -301,7 +303,6 @@ hipError_t launch_iow03(const Frame &f, const IowScene &sc, const Chunk &ch, con
 hipError_t launch_inw(const Frame &f, const InwScene &sc, const Chunk &ch, const Cont &ct, uint32_t n_units,
                       unsigned *counter, int blocks_cap, hipStream_t s);
 uint32_t units_of(const Frame &f);
-// resident 256-thread blocks per CU for the persistent kernels (occupancy query)
 // sample-parallel IOW-03 pass over the units of `mode` (kSpec*)
 hipError_t launch_iow03_spec(const Frame &f, const IowScene &sc, const SpecRecs &R, int mode, const Cont &ct,
                              uint32_t n_units, unsigned *counter, int blocks_cap, hipStream_t s);
@@ -404,8 +405,6 @@ hipError_t launch_iow03_prep(const Frame &f, const SpecRecs &R, unsigned *key, f
 // the rest (with their resume state in `state`) to the sequential kernel via R.fb_list
 hipError_t launch_iow03_resolve(const Frame &f, const SpecRecs &R, bool final_pass, float4 *state, hipStream_t s);
 
-// sample-parallel INW over samples [s0, s0+ns) of every pixel (records indexed (s-s0)*P + pu),
-// then End() over that chunk: carry the sum in `state` or write the pixels
 // INW with the on-chip End() folds (k_inw_probe + k_inw_pm / k_inw_sm); ring:
 // blocks * (kBlock / 64) * max(ring_pm, ring_sm) float4 (powers of two >= 64); counter: 2 queue
 // counters 64 B apart; mode: 2 uints; force: 0 = probe decides, 1 = pixel-major, 2 = sample-major
@@ -472,10 +471,28 @@ hipError_t launch_pixel_fold(const Frame &f, bool iow, const int2 *pixels, uint3
 // {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of k_camera_rays (which = 0 INW, 1
 // IOW-03) and k_pixel_fold (2 INW, 3 IOW-03)
 hipError_t pixels_kernel_info(int which, int info[4]);
-// resident blocks per CU of the render kernel for `kind` (3 = IOW-03 wide, 4 = IOW-03 narrow,
-// 11/14 = INW layout 1/4)
-int resident_blocks_per_cu(int kind);  // 5 = sample-parallel IOW-03, 6/7 = sample-parallel INW 1/4,
-                                       // 8 = asynchronous-window IOW-03
+// The persistent render kernels, by name, and the resident blocks per CU of each (occupancy query;
+// 2 if it fails).  The kernels are private to their units, so resident_blocks_per_cu
+// (rt_iow_render.hip) asks the unit that owns the kernel.
+enum class RenderKernel {
+    Iow03,         // k_iow03
+    Iow03Narrow,   // k_iow03n
+    Iow03Lds,      // k_iow03L (768-lane blocks)
+    Iow03Spec,     // k_iow03s
+    Iow03SpecLds,  // k_iow03sL (768-lane blocks)
+    Inw01,         // k_inw<false>
+    Inw04,         // k_inw<true>
+    InwPm01,       // k_inw_pm<false>
+    InwPm04,       // k_inw_pm<true>
+    InwPmLn01,     // k_inw_pm<false, true> (768-lane blocks)
+    InwPmLn04,     // k_inw_pm<true, true> (768-lane blocks)
+    InwPmGq,       // k_inw_pm<false, true, true, true, true> (kGqSub * 256-lane blocks)
+};
+int resident_blocks_per_cu(RenderKernel k);
+int iow_render_blocks_per_cu(RenderKernel k);  // rt_iow_render.hip: Iow03, Iow03Narrow, Iow03Lds
+int iow_spec_blocks_per_cu(RenderKernel k);    // rt_iow_spec.hip: Iow03Spec, Iow03SpecLds
+int inw_render_blocks_per_cu(RenderKernel k);  // rt_inw_render.hip: Inw01, Inw04
+int inw_fold_blocks_per_cu(RenderKernel k);    // rt_inw_fold.hip: InwPm*
 // IOW-03 kernel variant for this frame: narrow (byte bounce counts, 12-deep BVH stack, 4 waves
 // per SIMD with spills) when rt_options.iow_narrow and u_NumOfBounce <= 255; wide otherwise
 bool iow_narrow(const Frame &f);

@@ -143,13 +143,15 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     const rt_options &o = s->opt;
     const InwWalk &w = s->walk;
     InwFold &fold = s->fold;
-    const int blocks = s->cus * rtk::resident_blocks_per_cu(s->layout == 4 ? 16 : 15);
+    const int blocks = s->cus * rtk::resident_blocks_per_cu(s->layout == 4 ? rtk::RenderKernel::InwPm04 : rtk::RenderKernel::InwPm01);
     // the top of the wide BVH staged in LDS (768-lane blocks, 3 waves per SIMD);
     // inw_lds_nodes = 0: 256-lane blocks reading every node from L1 / L2 (A/B)
     // (without the wide walk the stackless LBVH walks read the top of the LBVH from that LDS; the
     // stack walks run in the same 768-lane instances, with nothing staged)
     const int blocks_ln = o.inw_lds_nodes && (w.n_wnodes || w.dfs_high)
-                              ? s->cus * rtk::resident_blocks_per_cu(s->layout == 4 ? 18 : 17) : 0;
+                              ? s->cus * rtk::resident_blocks_per_cu(s->layout == 4 ? rtk::RenderKernel::InwPmLn04
+                                                                                    : rtk::RenderKernel::InwPmLn01)
+                              : 0;
     // inw_ring_pm = 0: k_inw_pm's fold ring in LDS (768-lane blocks), else a global
     // ring of that many entries per wave (1024 for the 256-lane blocks)
     const bool lring = o.inw_ring_pm == 0 && blocks_ln > 0;
@@ -189,7 +191,7 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     // memory -- INW-01, the LDS ring instances, the fused cull's error bound (the quantised decode
     // is argued under it)
     if (o.inw_qnodes && s->layout != 4 && lring && sc.fused && sc.wnodes && w.qnodes.p) {
-        const uint32_t gb = uint32_t(s->cus * rtk::resident_blocks_per_cu(19));
+        const uint32_t gb = uint32_t(s->cus * rtk::resident_blocks_per_cu(rtk::RenderKernel::InwPmGq));
         const size_t need = size_t(gb) * rtk::kGqSub * rtk::kBlock * (rtk::kFStack / 4) * sizeof(float4);
         if (fold.gstk.reserve(need) != hipSuccess) return RT_E_HIP;
         sc.qnodes = w.qnodes.as<float4>();
@@ -306,7 +308,9 @@ int launch_scene(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     const rtk::IowScene iow = iow_view(*s);
     const rtk::InwScene inw = inw_view(*s);
     // grid of this frame's kernel variant
-    int cap = s->kind == 3 ? s->cus * rtk::resident_blocks_per_cu(rtk::iow_narrow(f) ? 4 : 3) : s->blocks_cap;
+    int cap = s->kind == 3 ? s->cus * rtk::resident_blocks_per_cu(rtk::iow_narrow(f) ? rtk::RenderKernel::Iow03Narrow
+                                                                                         : rtk::RenderKernel::Iow03)
+                           : s->blocks_cap;
     LastRender last;
     const char *kernel = s->kind == 3 ? (rtk::iow_narrow(f) ? "k_iow03n" : "k_iow03") : (s->layout == 4 ? "k_inw<true>" : "k_inw<false>");
     last.launches = int(plan.size()) * (1 + rounds);
@@ -316,7 +320,7 @@ int launch_scene(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     last.path.stackless = s->kind != 3 && s->walk.dfs_high != 0 && s->walk.sl_ok && s->opt.inw_stackless;
     if (s->kind == 3 && !rtk::iow_narrow(f)) {
         if (rtk::iow_lds(iow)) {
-            cap = s->cus * 3 * rtk::resident_blocks_per_cu(9);  // 256-lane slots of the 768-lane blocks
+            cap = s->cus * 3 * rtk::resident_blocks_per_cu(rtk::RenderKernel::Iow03Lds);  // 256-lane slots of the 768-lane blocks
             kernel = "k_iow03L";
         }
         last.path.iow_bvh = s->iow.root_link ? (rtk::iow_lds(iow) ? 2 : 1) : 0;

@@ -193,8 +193,10 @@ int launch_scene_spec(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     const rtk::IowScene scene = iow_view(*s);
     // caps in 256-lane slots; the LDS-BVH kernels run 768-lane blocks
     const bool lds = rtk::iow_lds(scene);
-    const int cap_s = s->cus * (lds ? 3 * rtk::resident_blocks_per_cu(10) : rtk::resident_blocks_per_cu(5));
-    const int cap_q = s->cus * (lds ? 3 * rtk::resident_blocks_per_cu(9) : rtk::resident_blocks_per_cu(3));
+    const int cap_s = s->cus * (lds ? 3 * rtk::resident_blocks_per_cu(rtk::RenderKernel::Iow03SpecLds)
+                                     : rtk::resident_blocks_per_cu(rtk::RenderKernel::Iow03Spec));
+    const int cap_q = s->cus * (lds ? 3 * rtk::resident_blocks_per_cu(rtk::RenderKernel::Iow03Lds)
+                                     : rtk::resident_blocks_per_cu(rtk::RenderKernel::Iow03));
     hipError_t e = hipSuccess;
     const bool spread_last = o.spec_spread != 0;
     // one compacted pass (run_rounds) of the speculative kernel over n0 units on queue q

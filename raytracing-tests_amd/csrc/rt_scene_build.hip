@@ -42,11 +42,14 @@ void set_residency(rt_dev_scene *s) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     s->cus = cus;
-    s->blocks_cap = cus * rtk::resident_blocks_per_cu(s->kind);
+    using rtk::RenderKernel;
+    const RenderKernel own = s->kind == 3 ? RenderKernel::Iow03 : (s->kind == 14 ? RenderKernel::Inw04 : RenderKernel::Inw01);
+    s->blocks_cap = cus * rtk::resident_blocks_per_cu(own);
     if (s->kind == 3)  // continuation buffers serve every IOW-03 variant
-        s->blocks_cap = std::max({s->blocks_cap, cus * rtk::resident_blocks_per_cu(4), cus * rtk::resident_blocks_per_cu(5)});
-    else  // and every INW variant
-        s->blocks_cap = std::max(s->blocks_cap, cus * rtk::resident_blocks_per_cu(s->kind == 14 ? 7 : 6));
+        s->blocks_cap = std::max({s->blocks_cap, cus * rtk::resident_blocks_per_cu(RenderKernel::Iow03Narrow),
+                                  cus * rtk::resident_blocks_per_cu(RenderKernel::Iow03Spec)});
+    else  // and the INW-01 per-pixel kernel
+        s->blocks_cap = std::max(s->blocks_cap, cus * rtk::resident_blocks_per_cu(RenderKernel::Inw01));
 }
 
 // u_MaterialTextures[0..n_tex) (04...glsl:10; bound by GeometryData_04::BindExtraData,

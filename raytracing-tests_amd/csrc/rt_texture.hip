@@ -1,5 +1,5 @@
 // Texture producers of SURVEY 8f2 on the GPU (the texture SAMPLING lives in the INW kernel,
-// rt_kernels.hip inw_tex_color):
+// rt_inw_shade.hpp inw_tex_color):
 //   - noise textures: Helper::Noise::MakeTexture<glm::vec3> (Utilities/utility.h:69-192) with
 //     Snoise2 / Fbm2 / Turbulance (Utilities/utility.cpp:609-769);
 //   - the Mercator <-> cubic re-projection of TEXTURE_2D::LoadFromDiskToGPU

@@ -28,7 +28,7 @@ def _no_lights(sc):
 def _touching_cuboids(n=25, **over):
     """INW-01 with unit cubes at unit spacing on the grid stage's layout: neighbouring cubes share
     faces, and every face lies on its LBVH leaf box, where rounding can put an object's hit an ulp
-    before its box's entry t (the wide walk's leaf-entry guard, rt_kernels.hip inw_traverse_wide)."""
+    before its box's entry t (the wide walk's leaf-entry guard, rt_inw_walk.hpp inw_traverse_wide)."""
     sc = R.make_scene(R.PRESET_INW01_GRID, 0, n, **over)
     arr = sc.desc
     for i in range(sc.n):

@@ -1,4 +1,4 @@
-"""A CPU model of k_inw_pm's wave scheduler (raytracing-tests_amd/csrc/rt_kernels.hip, k_inw_pm):
+"""A CPU model of k_inw_pm's wave scheduler (raytracing-tests_amd/csrc/rt_inw_fold.hip, k_inw_pm):
 pixel claims at most 64 ordinals ahead of the fold, issue of stream entries g = (pixel ordinal,
 sample) to free lanes within the fold window, the LDS ring's finished-entry rule (every issued
 entry below the smallest one a busy lane holds is stored), the in-order fold (01_BVH...glsl:

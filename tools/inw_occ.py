@@ -2,7 +2,7 @@
     make -C raytracing-tests_amd variant VARIANT=occ VDEFS=-DRT_DIAG_OCC
     RT_HIP_LIB=raytracing-tests_amd/librt_hip_occ.so python tools/inw_occ.py [c3|c5] [spp] [FIELD=VALUE ...]
 Prints, per phase, the wave iterations, the lanes doing that phase's work per iteration (of 64)
-and the share of wave iterations; slots as rt_kernels.hip kOcc*."""
+and the share of wave iterations; slots as rt_inw_walk.hpp kOcc*."""
 import ctypes as C
 import json
 import os

@@ -1,12 +1,12 @@
 #!/bin/bash
 # Kernel resource usage (VGPRs, SGPRs, spills, LDS) of the gfx950 code object inside a built
-# object file: tools/kres.sh [build/rt_kernels.o] [name-regex]
+# object file: tools/kres.sh [build/rt_inw_fold.o] [name-regex]
 set -e
-OBJ=${1:-raytracing-tests_amd/build/rt_kernels.o}
+OBJ=${1:-raytracing-tests_amd/build/rt_inw_fold.o}
 PAT=${2:-inw_pm|inw_sm}
 LLVM=/opt/rocm/lib/llvm/bin
 T=$(mktemp -d)
-$LLVM/llvm-objcopy --dump-section=.hip_fatbin=$T/fat.bin "$OBJ"
+$LLVM/llvm-objcopy --dump-section=.hip_fatbin=$T/fat.bin "$OBJ" $T/copy.o  # (no output path: rewrites $OBJ in place)
 $LLVM/clang-offload-bundler --unbundle --type=o --input=$T/fat.bin \
     --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=$T/k.co
 $LLVM/llvm-readelf --notes $T/k.co | grep -E "^ +\.(name|vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size|private_segment_fixed_size):" |

@@ -1,6 +1,6 @@
 """Static instruction census of the loops of one kernel in a gfx950 assembly listing.
 
-    hipcc <the Makefile's flags> --offload-device-only -S csrc/rt_kernels.hip -o k.s
+    hipcc <the Makefile's flags> --offload-device-only -S csrc/rt_inw_fold.hip -o k.s
     python tools/loop_census.py k.s 'k_inw_pmILb0ELb1ELb1ELb1ELb0' [--has buffer_load_dwordx4=7] [--cut global_load]
 
 A loop is the text from a label to a later branch back to it.  Every loop of the kernel is listed
