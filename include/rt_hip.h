@@ -633,6 +633,69 @@ int rt_pixels_iow03(const float *types, const float *records /* N*24 */, uint32_
                     const rt_params *p, const rt_pixel *pixels, uint32_t n_pixels, rt_path_iow_ray *rays_out,
                     rt_path_iow_out *samples_out, rt_pixel_out *pixels_out, int device, rt_stats *st);
 
+/* ---- progressive sample passes ---------------------------------------------------------------
+ * Refinement in samples: the host renders samples [0, 8) of every pixel and shows them, then [8, 40)
+ * and shows the better image, and so on; after the last range it holds, bit for bit, the frame
+ * rt_render_image_async would have written.  The folds allow it exactly: INW's End()
+ * (01_BoundingVolumeHierarchy/computeShaderSrc.glsl:625-675) is a sequential float sum in sample
+ * order (the first sqrt(colour) assigned, the others added, the sum times RN(1 / spp)), IOW-03's
+ * out_Pixel (03_Shadows_and_Materials/computeShaderSrc.glsl:383-417) a sequential sum from 0, and an
+ * IOW-03 sample inherits exactly four floats from its predecessor, the RI fields of the ray-stack
+ * slots (rt_path_iow_rays_async's ri_in / ri_out).  Cutting the sample loop anywhere changes no bit.
+ *
+ * rt_render_pass_async renders samples [s0, min(s0 + ns, S)) of every pixel of the rectangle
+ * p->tile_* (the whole frame when tile_w or tile_h is 0), exactly as rt_render_image_async reads
+ * that rectangle.  S = spp on an INW scene; on an IOW-03 scene S is the first sample whose ring entry
+ * is the shader's early-return marker (03...glsl:396), else spp (no table rt_sample_tables builds has
+ * such a marker).
+ *   - State: d_state[y * W + x] is the pixel's state after samples [0, s0); the pass leaves it as the
+ *     state after [0, min(s0 + ns, S)).  INW: acc = End()'s running sum, depth = the depth of sample
+ *     spp / 2 once that sample has run, else 0; ri is neither read nor written.  IOW-03: acc = the
+ *     running sum, depth = 0, ri = the RI fields of the four stack slots as the last sample left
+ *     them.  With s0 == 0 the incoming state is not read (no memset is needed): INW assigns the
+ *     first sample, IOW-03 starts from 0 with ri = 0.  The caller issues the passes of a frame in
+ *     order, with s0 equal to the samples already in the state; the call cannot check this.
+ *   - Image: when d_rgba is given, the pixel's value is acc * RN(1 / k) with alpha 1, k = min(s0 +
+ *     ns, S): the frame as it would be at k samples of these tables.  At k == S it is the frame
+ *     rt_render_image_async writes, bit for bit; so is d_depth (INW: the state's depth; IOW-03: 0).
+ *     Pixels outside the rectangle keep their state and image bytes.
+ *   - counters: added to as the renders count them; summed over the passes of a frame, [0], [3], [4]
+ *     and [5] (INW) or [0], [4] and [5] (IOW-03) are the render's; [1], [2] are this build's own.
+ *   - The scene's options apply (wide walk, time bins, sphere records, stackless walks, fused cull,
+ *     iow_linear, iow_lds_bvh, iow_leaf_batch); the result is bit-identical whatever they are.  A
+ *     scene updated by rt_dev_scene_inw_update / rt_dev_scene_iow03_update behaves as a fresh one.
+ *   - Never synchronises.  On an IOW-03 scene it never allocates; on an INW scene a pass is, per chunk
+ *     of samples, the camera rays, rt_path_rays_async's kernel on them and the fold, in a workspace the
+ *     scene owns (64 B per pixel unit and sample of a chunk, at most 2 GB unless one sample of the
+ *     rectangle needs more): the first pass of a rectangle size and sample count grows it, as the
+ *     first render of a frame size allocates, and later passes allocate nothing, so they are
+ *     graph-capturable.  Calls on one scene must not overlap each other, its renders or its queries.
+ * Returns RT_E_ARG, before a device is touched and with the buffers untouched, for a null scene, cam,
+ * p or d_state, bad params as the renders judge them, p->spp != the scene's, s0 >= p->spp or a scene
+ * a failed update left broken; then RT_E_UNSUPPORTED for p->show_normal != 0.  ns == 0 returns RT_OK
+ * and launches nothing; s0 + ns may overrun S (the pass is clipped).  Not covered: packed tile lists,
+ * device groups and the MULTIFOCUS camera (no device scene has one: only rt_render_inw_mf's own). */
+typedef struct rt_pass_state { float acc[3]; float depth; float ri[4]; } rt_pass_state;   /* 32 B */
+/* Device pointers (16-byte aligned). */
+int rt_render_pass_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p,
+                         uint32_t s0, uint32_t ns, rt_pass_state *d_state /* W*H */,
+                         float *d_rgba /* W*H*4, may be NULL */, float *d_depth /* W*H, may be NULL */,
+                         uint64_t *d_counters /* 6 x u64, added to; may be NULL */, void *stream);
+/* Blocking: host buffers; build a device scene for the call like rt_pixels_inw / rt_pixels_iow03.
+ * cuts is strictly increasing with cuts[0] > 0 and cuts[n_cuts - 1] <= p->spp; pass i renders
+ * [cuts[i - 1], cuts[i]) (from 0 for i = 0) and image i (rgba + i * W*H*4, depth + i * W*H) is the
+ * image after it; pixels outside the rectangle keep the bytes the buffers came with.  state_out (may
+ * be NULL): the state after the last pass.  st (may be NULL): the counters and the passes' device
+ * time.  RT_E_ARG also for null rgba or bad cuts. */
+int rt_render_passes_inw(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                         uint32_t n_lights, const rt_texture *tex, int n_tex, const rt_camera *cam,
+                         const rt_params *p, const uint32_t *cuts, int n_cuts,
+                         float *rgba /* n_cuts*W*H*4 */, float *depth /* n_cuts*W*H or NULL */,
+                         rt_pass_state *state_out /* W*H, may be NULL */, int device, rt_stats *st);
+int rt_render_passes_iow03(const float *types, const float *records /* N*24 */, uint32_t n, const rt_camera *cam,
+                           const rt_params *p, const uint32_t *cuts, int n_cuts, float *rgba /* n_cuts*W*H*4 */,
+                           rt_pass_state *state_out /* W*H, may be NULL */, int device, rt_stats *st);
+
 /* ---- multi-GPU partition (BASELINE configs[3]) -----------------------------
  * One host thread drives several devices of this process: the frame's tiles are dealt
  * across the devices, each renders its share with rt_render_tiles_async on a stream of its own,

@@ -189,6 +189,15 @@ int rt_debug_path_iow_max_blocks(int blocks);
  * k_camera_rays on an INW scene, 1 on an IOW-03 scene, 2 k_pixel_fold INW, 3 IOW-03 (blocks of 256
  * lanes: 256 records of rays, four pixels of the fold).  RT_E_ARG for any other `which`. */
 int rt_debug_pixels_kernel(int which, int info[4]);
+/* The same pair for the progressive-pass kernels (rt_render_pass_async).  An INW pass is the camera
+ * rays of its samples, the path-query kernel (rt_debug_paths_kernel) and the fold: which = 0 is
+ * k_pass_rays, 1 k_pass_fold, both serving INW-01 and INW-04 alike; 2 is the IOW-03 kernel with the BVH
+ * staged in LDS, 3 the one that reads nodes from global memory (also the linear loop's).  RT_E_ARG for
+ * any other `which`.  The cap counts 256-lane blocks of the kernels that own a lane per path or pixel
+ * (INW: the path-query kernel's grid during a pass; IOW-03: k_iow_pass's); rt_debug_pass_max_blocks
+ * returns the previous cap. */
+int rt_debug_pass_kernel(int which, int info[4]);
+int rt_debug_pass_max_blocks(int blocks);
 
 #ifdef __cplusplus
 }

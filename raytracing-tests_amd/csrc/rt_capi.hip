@@ -163,6 +163,60 @@ int pixels_blocking(const rt_camera *cam, const rt_params *p, const rt_pixel *pi
     return st ? read_stats(d_ctr.p, ms, st) : RT_OK;
 }
 
+// Progressive passes: cuts is strictly increasing from cuts[0] > 0 to at most spp.
+bool cuts_ok(const rt_params *p, const uint32_t *cuts, int n_cuts) {
+    if (!cuts || n_cuts < 1 || cuts[0] == 0 || cuts[n_cuts - 1] > uint32_t(p->spp)) return false;
+    for (int i = 1; i < n_cuts; i++)
+        if (cuts[i] <= cuts[i - 1]) return false;
+    return true;
+}
+
+// The blocking passes: a temporary scene from make(scene), the host buffers up (pixels outside the
+// rectangle keep their bytes), pass i = samples [cuts[i - 1], cuts[i]) into image i, timed together
+// on the null stream, the images, the last state and the counters back.
+template <class Make>
+int passes_blocking(const rt_camera *cam, const rt_params *p, const uint32_t *cuts, int n_cuts, float *rgba,
+                    float *depth, rt_pass_state *state_out, int device, rt_stats *st, Make &&make) {
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    std::unique_ptr<rt_dev_scene> s = temp_scene();
+    if (!s) return RT_E_ARG;
+    try {  // the host builders allocate: no exception crosses the ABI
+        rc = make(s.get());
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    if (rc != RT_OK) return rc;
+    if (st) std::memset(st, 0, sizeof(*st));
+    const size_t npx = size_t(p->width) * size_t(p->height);
+    DevBuf d_state, d_rgba, d_depth, d_ctr;
+    if (state_out) HIP_OK(d_state.upload(state_out, npx * sizeof(rt_pass_state)));
+    else HIP_OK(d_state.alloc(npx * sizeof(rt_pass_state)));
+    HIP_OK(d_rgba.upload(rgba, size_t(n_cuts) * npx * 16));
+    if (depth) HIP_OK(d_depth.upload(depth, size_t(n_cuts) * npx * 4));
+    HIP_OK(d_ctr.alloc(6 * sizeof(unsigned long long)));
+    HIP_OK(hipMemset(d_ctr.p, 0, 6 * sizeof(unsigned long long)));
+    double ms = 0.0;
+    rc = timed([&] {
+        uint32_t s0 = 0;
+        for (int i = 0; i < n_cuts; i++) {
+            const int r = rt_render_pass_async(s.get(), cam, p, s0, cuts[i] - s0, d_state.as<rt_pass_state>(),
+                                               d_rgba.as<float>() + size_t(i) * npx * 4,
+                                               depth ? d_depth.as<float>() + size_t(i) * npx : nullptr,
+                                               d_ctr.as<uint64_t>(), nullptr);
+            if (r != RT_OK) return r;
+            s0 = cuts[i];
+        }
+        return int(RT_OK);
+    }, &ms);
+    if (rc != RT_OK) return rc;
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(rgba, d_rgba.p, size_t(n_cuts) * npx * 16, hipMemcpyDeviceToHost));
+    if (depth) HIP_OK(hipMemcpy(depth, d_depth.p, size_t(n_cuts) * npx * 4, hipMemcpyDeviceToHost));
+    if (state_out) HIP_OK(hipMemcpy(state_out, d_state.p, npx * sizeof(rt_pass_state), hipMemcpyDeviceToHost));
+    return st ? read_stats(d_ctr.p, ms, st) : RT_OK;
+}
+
 }  // namespace
 
 rt_options g_opt = default_options();
@@ -754,6 +808,84 @@ int rt_pixels_iow03(const float *types, const float *records, uint32_t n, const 
     if (!pixels_args_ok(p, pixels, n_pixels, pixels_out)) return RT_E_ARG;
     if (p->show_normal) return RT_E_UNSUPPORTED;
     return pixels_blocking(cam, p, pixels, n_pixels, rays_out, samples_out, pixels_out, device, st,
+                           [&](rt_dev_scene *s) { return make_iow03(s, types, records, n, p->spp); });
+}
+
+// ------------------------------------------------------------------------ progressive passes
+int rt_render_pass_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p, uint32_t s0, uint32_t ns,
+                         rt_pass_state *d_state, float *d_rgba, float *d_depth, uint64_t *d_counters, void *stream) {
+    static_assert(sizeof(rt_pass_state) == 32, "rt_pass_state is 2 float4");
+    if (!s || !cam || !params_ok(p) || !d_state || p->spp != s->spp || s0 >= uint32_t(p->spp) || s->broken)
+        return RT_E_ARG;
+    if (p->show_normal) return RT_E_UNSUPPORTED;  // one normal per sample, no fold state
+    if (ns == 0) return RT_OK;
+    const bool iow = s->kind == 3;
+    // the samples the shader runs: IOW-03 stops at the ring schedule's early return (k_iow03's s_stop)
+    const uint32_t stop = uint32_t(iow ? s->s_stop : s->spp);
+    const uint32_t s1 = uint32_t(std::min<uint64_t>(uint64_t(s0) + ns, stop));
+    rtk::Frame f = make_frame(cam, p);
+    f.out_rgba = d_rgba; f.out_depth = d_depth;
+    f.counters = reinterpret_cast<unsigned long long *>(d_counters);
+    f.dbg = nullptr; f.px_rays = nullptr;  // the renders' diagnostics hooks do not apply
+    f.leaf_batch = s->opt.iow_leaf_batch;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    float4 *state = reinterpret_cast<float4 *>(d_state);
+    if (iow) {
+        // its own queue counter: clear of the fold kernels' (bytes 0..767) and the queries' (words 208, 224, 240)
+        unsigned *queue = s->counter.as<unsigned>() + 192;
+        const hipError_t e = rtk::launch_iow_pass(f, iow_view(*s), s0, s1, state, queue, s->cus, st);
+        return e == hipSuccess ? RT_OK : launch_failed(e);
+    }
+    // INW: per chunk of samples, the camera rays into the scene's pass workspace, the path queries on them
+    // (rt_path_rays_async's launch: its scene view, its queue word, its fused-cull rule) and the fold.
+    // A chunk is as many samples as keep the rays and answers (64 B a sample and unit) within kPassRecords
+    // records; the first pass of a frame size and chunk grows the workspace, later ones allocate nothing.
+    constexpr uint64_t kPassRecords = uint64_t(1) << 25;
+    const uint32_t units = rtk::units_of(f);
+    if (units == 0 || units > (1u << 31)) return RT_E_ARG;
+    const uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(s1 - s0, kPassRecords / units)));
+    HIP_OK(s->pass_ws.reserve(size_t(units) * chunk * 2 * sizeof(rt_path_ray)));
+    float4 *rays = s->pass_ws.as<float4>(), *out = rays + size_t(units) * chunk * 2;
+    rtk::InwScene sc = inw_view(*s);
+    if (s->layout == 4) sc.sph = nullptr;
+    sc.fused = (s->opt.inw_fused_cull && sc.wnodes && s->walk.wbound <= 1000.0f) ? 1 : 0;
+    // the frame's child order: dot(dir, (1, 1, 1)) > 0 in binary32, the shader's order (inw_segment)
+    const float dsum = (cam->dir[0] * 1.0f + cam->dir[1] * 1.0f) + cam->dir[2] * 1.0f;
+    unsigned *queue = s->counter.as<unsigned>() + 224;
+    const int cap = rtk::inw_paths_max_blocks(rtk::pass_max_blocks_now());  // rt_debug_pass_max_blocks caps the paths' grid
+    hipError_t e = hipSuccess;
+    for (uint32_t c0 = s0; c0 < s1 && e == hipSuccess; c0 += chunk) {
+        const uint32_t nsc = std::min(chunk, s1 - c0);
+        e = rtk::launch_pass_rays(f, sc, c0, nsc, rays, st);
+        if (e == hipSuccess)
+            e = rtk::launch_inw_paths(sc, rays, units * nsc, s->spp, p->max_bounces, dsum > 0.0f, out,
+                                      reinterpret_cast<unsigned long long *>(d_counters), queue, s->cus, st);
+        if (e == hipSuccess) e = rtk::launch_pass_fold(f, c0, nsc, c0 + nsc == s1 ? s1 : 0u, out, state, st);
+    }
+    (void)rtk::inw_paths_max_blocks(cap);
+    return e == hipSuccess ? RT_OK : launch_failed(e);
+}
+
+int rt_render_passes_inw(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                         uint32_t n_lights, const rt_texture *tex, int n_tex, const rt_camera *cam, const rt_params *p,
+                         const uint32_t *cuts, int n_cuts, float *rgba, float *depth, rt_pass_state *state_out,
+                         int device, rt_stats *st) {
+    if (!geom || !nodes || n == 0 || (layout != 1 && layout != 4) || !cam || !params_ok(p) || !rgba) return RT_E_ARG;
+    if (layout == 4 && n_lights > 0 && !lights) return RT_E_ARG;
+    if (!textures_ok(tex, n_tex) || !cuts_ok(p, cuts, n_cuts)) return RT_E_ARG;
+    if (n_tex == 0 && inw_textured(geom, n, layout)) return RT_E_UNSUPPORTED;  // no texture bound
+    if (p->show_normal) return RT_E_UNSUPPORTED;
+    return passes_blocking(cam, p, cuts, n_cuts, rgba, depth, state_out, device, st, [&](rt_dev_scene *s) {
+        return make_inw(s, geom, n, layout, nodes, lights, n_lights, tex, n_tex, p->spp);
+    });
+}
+
+int rt_render_passes_iow03(const float *types, const float *records, uint32_t n, const rt_camera *cam,
+                           const rt_params *p, const uint32_t *cuts, int n_cuts, float *rgba,
+                           rt_pass_state *state_out, int device, rt_stats *st) {
+    if (!types || !records || n == 0 || !cam || !params_ok(p) || !rgba || !cuts_ok(p, cuts, n_cuts)) return RT_E_ARG;
+    if (p->show_normal) return RT_E_UNSUPPORTED;
+    return passes_blocking(cam, p, cuts, n_cuts, rgba, nullptr, state_out, device, st,
                            [&](rt_dev_scene *s) { return make_iow03(s, types, records, n, p->spp); });
 }
 

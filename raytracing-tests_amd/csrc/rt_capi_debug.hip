@@ -443,4 +443,12 @@ int rt_debug_pixels_kernel(int which, int info[4]) {
     return RT_OK;
 }
 
+int rt_debug_pass_kernel(int which, int info[4]) {
+    if (!info || which < 0 || which > 3) return RT_E_ARG;
+    HIP_OK(rtk::pass_kernel_info(which, info));
+    return RT_OK;
+}
+
+int rt_debug_pass_max_blocks(int blocks) { return rtk::pass_max_blocks(blocks); }
+
 }  // extern "C"

@@ -471,6 +471,27 @@ hipError_t launch_pixel_fold(const Frame &f, bool iow, const int2 *pixels, uint3
 // {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of k_camera_rays (which = 0 INW, 1
 // IOW-03) and k_pixel_fold (2 INW, 3 IOW-03)
 hipError_t pixels_kernel_info(int which, int info[4]);
+// rt_passes.hip, IOW-03: samples [s0, s1) of every pixel of f's rectangle (rect mode; f.out_rgba and
+// f.out_depth may be null, f.counters is added to) on a persistent grid of at most cus * resident
+// blocks, a lane per pixel; state: 2 float4 per pixel of the W x H image (rt_pass_state), read when
+// s0 > 0 and left as the state after sample s1 - 1; queue: one u32 (zeroed here).  s1 <= the scene's
+// s_stop, f.leaf_batch set, iow_lds(sc) picks the LDS-staged instance.
+hipError_t launch_iow_pass(const Frame &f, const IowScene &sc, uint32_t s0, uint32_t s1, float4 *state,
+                           unsigned *queue, int cus, hipStream_t s);
+// rt_passes.hip, INW: the two ends of a pass around launch_inw_paths.  The camera rays of samples
+// [s0, s0 + ns) of every unit of f's rectangle as path queries, record u * ns + j = unit u, sample
+// s0 + j (units_of(f) * ns <= 2^31 records of 2 float4); and End()'s fold of the answers into the state
+// (the first float4 of a pixel's rt_pass_state; read when s0 > 0), with the image acc * RN(1 / k) and
+// the depth written when k > 0.
+hipError_t launch_pass_rays(const Frame &f, const InwScene &sc, uint32_t s0, uint32_t ns, float4 *rays,
+                            hipStream_t s);
+hipError_t launch_pass_fold(const Frame &f, uint32_t s0, uint32_t ns, uint32_t k, const float4 *out, float4 *state,
+                            hipStream_t s);
+// {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of k_pass_rays (which = 0), k_pass_fold
+// (1) and k_iow_pass (2 nodes staged in LDS, 3 not)
+hipError_t pass_kernel_info(int which, int info[4]);
+int pass_max_blocks_now();        // the cap rt_debug_pass_max_blocks set (0 = none)
+int pass_max_blocks(int blocks);  // rt_debug_pass_max_blocks: cap the grid (0 = off); the previous cap
 // The persistent render kernels, by name, and the resident blocks per CU of each (occupancy query;
 // 2 if it fails).  The kernels are private to their units, so resident_blocks_per_cu
 // (rt_iow_render.hip) asks the unit that owns the kernel.

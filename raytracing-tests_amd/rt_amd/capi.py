@@ -231,6 +231,15 @@ SIGNATURES = {
     "rt_pixels_iow03": (C.c_int, [_FP, _FP, C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_void_p,
                                   C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RtStats)]),
     "rt_debug_pixels_kernel": (C.c_int, [C.c_int, _IP]),
+    "rt_render_pass_async": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_passes_inw": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtTexture), C.c_int,
+                                       C.POINTER(RtCamera), C.POINTER(RtParams), _U32P, C.c_int, _FP, _FP,
+                                       C.c_void_p, C.c_int, C.POINTER(RtStats)]),
+    "rt_render_passes_iow03": (C.c_int, [_FP, _FP, C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtParams), _U32P,
+                                         C.c_int, _FP, C.c_void_p, C.c_int, C.POINTER(RtStats)]),
+    "rt_debug_pass_kernel": (C.c_int, [C.c_int, _IP]),
+    "rt_debug_pass_max_blocks": (C.c_int, [C.c_int]),
     "rt_render_multi_async": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
@@ -896,6 +905,63 @@ def pixels_kernel_info(which: int) -> dict:
     """rt_debug_pixels_kernel: registers, scratch, LDS and resident blocks per CU of PIXELS_KERNELS[which]."""
     info = (C.c_int * 4)()
     check(load().rt_debug_pixels_kernel(int(which), info), "rt_debug_pixels_kernel")
+    return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
+
+
+# ------------------------------------------------------------- progressive passes
+# rt_pass_state (include/rt_hip.h), 32 bytes
+PASS_STATE_DTYPE = np.dtype([("acc", np.float32, 3), ("depth", np.float32), ("ri", np.float32, 4)])
+
+
+def render_passes(sc: Scene, cuts, want_state: bool = False, params: RtParams | None = None, rgba=None, depth=None,
+                  state=None, device: int = -1) -> dict:
+    """rt_render_passes_inw / rt_render_passes_iow03: the blocking progressive passes of the frame
+    (sc.camera, params): pass i renders samples [cuts[i - 1], cuts[i]) of the rectangle params.tile_*.
+    Returns {"rgba": (n_cuts, H, W, 4), "depth": (n_cuts, H, W) or None on IOW-03, "stats": dict, and
+    with want_state "state": (H, W) PASS_STATE_DTYPE after the last pass}.  rgba, depth and state: arrays
+    of those shapes to start from (pixels outside the rectangle keep their bytes); default zeros."""
+    lib = load()
+    p = params or sc.params
+    iow = sc.stage == RT_STAGE_IOW03
+    cuts = np.ascontiguousarray(cuts, np.uint32).reshape(-1)
+    n, H, W = len(cuts), p.height, p.width
+    rgba = np.zeros((n, H, W, 4), np.float32) if rgba is None else np.ascontiguousarray(rgba, np.float32)
+    assert rgba.shape == (n, H, W, 4)
+    if iow:
+        depth = None
+    else:
+        depth = np.zeros((n, H, W), np.float32) if depth is None else np.ascontiguousarray(depth, np.float32)
+        assert depth.shape == (n, H, W)
+    if want_state:
+        state = np.zeros((H, W), PASS_STATE_DTYPE) if state is None else np.ascontiguousarray(state, PASS_STATE_DTYPE)
+        assert state.shape == (H, W)
+    st = RtStats()
+    tail = (state.ctypes.data if want_state else None, device, C.byref(st))
+    if iow:
+        check(lib.rt_render_passes_iow03(fptr(sc.types), fptr(sc.records), sc.n, C.byref(sc.camera), C.byref(p),
+                                         cuts.ctypes.data_as(_U32P), n, fptr(rgba), *tail), "rt_render_passes_iow03")
+    else:
+        lights = sc.lights if sc.lights is not None and len(sc.lights) else None
+        tex = getattr(sc, "textures", None) or []
+        arr, keep = texture_array(tex)
+        check(lib.rt_render_passes_inw(fptr(sc.geom), sc.n, sc.layout, fptr(sc.nodes), fptr(lights), sc.n_lights,
+                                       arr if tex else None, len(tex), C.byref(sc.camera), C.byref(p),
+                                       cuts.ctypes.data_as(_U32P), n, fptr(rgba), fptr(depth), *tail),
+              "rt_render_passes_inw")
+        del keep
+    res = {"rgba": rgba, "depth": depth, "stats": st.as_dict()}
+    if want_state:
+        res["state"] = state
+    return res
+
+
+PASS_KERNELS = ("k_pass_rays (INW)", "k_pass_fold (INW)", "k_iow_pass LDS nodes", "k_iow_pass global nodes")
+
+
+def pass_kernel_info(which: int) -> dict:
+    """rt_debug_pass_kernel: registers, scratch, LDS and resident blocks per CU of PASS_KERNELS[which]."""
+    info = (C.c_int * 4)()
+    check(load().rt_debug_pass_kernel(int(which), info), "rt_debug_pass_kernel")
     return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
 
 
