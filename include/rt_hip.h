@@ -175,6 +175,12 @@ typedef struct rt_options {
     int inw_sky_blocks;     /* INW-01, 1 (default): pixel-major frames render the 8x8 blocks whose pixels have empty,
                                complete beam lists (no primary ray can reach an object) in the lean kernel
                                k_inw_sky, outside k_inw_pm's claims (DESIGN.md §5.1 "Sky blocks") */
+    int inw_beam_prune;     /* what the beam lists leave out (DESIGN.md §5.2 "Pixel beams"): 0 nothing (every leaf
+                               whose box, inflated by the beam's largest radius, the central ray crosses);
+                               1: leaves whose box the central ray misses once it is inflated by the beam's
+                               radius over the box's own depth interval; 2 (default): also, in scenes with
+                               sphere records, spheres whose swept centre stays farther from the central
+                               line than their radius plus the beam's */
 } rt_options;
 void rt_options_default(rt_options *o);
 int  rt_options_set(const rt_options *o);   /* RT_E_ARG: null, wrong size or a value out of range */

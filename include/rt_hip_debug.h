@@ -37,6 +37,7 @@ typedef struct rt_path_info {
                              tree; inw_time_bins, moving objects, walks that read no LDS-staged nodes) */
     int beam_bins;        /* INW: beam lists per pixel (one per time bin; 0: one list over the swept boxes) */
     int sphere_records;   /* INW: 1 when the object tests read the sphere records (inw_sphere_records) */
+    int beam_prune;       /* INW: what the frame's beam lists left out (inw_beam_prune: 0, 1, or 2 with sphere records) */
 } rt_path_info;
 int rt_debug_path(rt_dev_scene *s, rt_path_info *out);
 /* Sky blocks of the scene's last INW fold render (rt_options.inw_sky_blocks; synchronises): out[0] =
@@ -45,6 +46,28 @@ int rt_debug_path(rt_dev_scene *s, rt_path_info *out);
  * k_inw_pm), out[2] = the frame's blocks.  A frame the path does not apply to reports 0 flagged.
  * s == NULL: the same of the last blocking render (rt_render_inw and its kin build a scene per call). */
 int rt_debug_sky_blocks(rt_dev_scene *s, uint32_t out[3]);
+/* The beam lists of the scene's last INW fold render (k_inw_beam's output; synchronises): totals =
+ * {lists (pixel units, padding included, x time bins), non-empty lists, entries, lists with a cut
+ * (some leaf not kept), lists switched off (the wide walk answers), entries a list can hold, 0, 0}.
+ * Each of n_out, cut_out (totals[0] values: a list's entry count, or 0xffffffff when switched off;
+ * its cut, +infinity when nothing was cut) and entries_out (totals[0] * totals[5] uint64,
+ * list l's entries at l * totals[5]: the object id in the low half, the stored key word in the high
+ * one -- the float bits of the entry t, or its high 16 bits when entries are packed) may be NULL;
+ * cap_lists says how many lists the others hold (RT_E_ARG when too few).  A frame without beam
+ * lists, or a sample-major one (no list written), reports totals[0] = 0. */
+int rt_debug_beam_lists(rt_dev_scene *s, uint64_t totals[8], uint32_t *n_out, float *cut_out, uint64_t *entries_out,
+                        uint32_t cap_lists);
+/* k_inw_beam's keep / drop decision for one culling box, on the host (no device; tests): the camera
+ * position, the pixel's central direction cd (inw_pixel_dir), aperture and focus distance of the
+ * frame, the lens table's largest |x| + |y| (sf_max) and the scene bound (wbound) give the beam as
+ * set_beam derives it; box = lo xyz, hi xyz; sph = the object's sphere record (8 floats: position,
+ * RN(1 / scale), position - last_position, RI) or NULL; bin of `bins` time bins (bins <= 1: one list
+ * over the shutter interval); prune = rt_options.inw_beam_prune.  Returns 1 when the list keeps the
+ * leaf, 0 when it does not, RT_E_ARG for a bad argument, RT_E_UNSUPPORTED when this camera gets no
+ * beam lists.  *candidate (may be NULL): 1 when the leaf passes the test of prune = 0. */
+int rt_beam_keep_host(const float cam_pos[3], const float cd[3], float aperture, float focus, float sf_max,
+                      float wbound, const float box[6], const float *sph, uint32_t bin, uint32_t bins, int prune,
+                      int *candidate);
 
 /* ---- diagnostics ---------------------------------------------------------------------
  * d_buf: device array of 16 uint64 (or NULL to disable).  While set, the IOW-03 kernel adds

@@ -34,6 +34,7 @@ rt_options default_options() {
     o.spec_alt_seg = 0; o.spec_alt_every = 0; o.spec_spread = 1; o.spec_prior_from = 2; o.spec_sort = 1;
     o.spec_solo = 4096; o.spec_validate = 1; o.spec_max_gb = 96.0;
     o.inw_sky_blocks = 1;
+    o.inw_beam_prune = 2;
     return o;
 }
 bool options_ok(const rt_options *o) {
@@ -45,7 +46,7 @@ bool options_ok(const rt_options *o) {
            o->spec_rounds >= 0 && o->spec_tail_rounds >= 0 && o->spec_tail_budget >= 1 && o->spec_scan >= 0 &&
            o->spec_alt_cap >= 1024 && o->spec_alt_cap <= (1 << 24) && o->spec_alt_seg >= 0 && o->spec_alt_every >= 0 &&
            o->spec_prior_from >= 1 && o->spec_solo >= 0 && o->spec_max_gb > 0.0 && o->inw_time_bins >= 0 &&
-           o->inw_time_bins <= 16;
+           o->inw_time_bins <= 16 && o->inw_beam_prune >= 0 && o->inw_beam_prune <= 2;
 }
 
 bool noise_args_ok(int width, int height, int type, const float *gradient, int n_grad, int octaves) {

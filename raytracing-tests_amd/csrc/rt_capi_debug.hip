@@ -2,6 +2,8 @@
 // what the tests ask about the last render.  No exception crosses the ABI.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -87,7 +89,7 @@ int rt_debug_path(rt_dev_scene *s, rt_path_info *out) {
             P.lds_nodes = L.lring_sm ? std::min(n_wtree0, rtk::kPmLdsNodes) : std::min(n_wtree0, uint32_t(rtk::kInwLdsNodes));
         }
     }
-    if (P.order != 1) { P.beams = 0; P.claim_order = 0; P.beam_bins = 0; }  // both serve the pixel-major kernel only
+    if (P.order != 1) { P.beams = 0; P.claim_order = 0; P.beam_bins = 0; P.beam_prune = 0; }  // both serve the pixel-major kernel only
     *out = P;
     return RT_OK;
 }
@@ -210,6 +212,84 @@ int rt_debug_sky_blocks(rt_dev_scene *s, uint32_t out[3]) {
     }
     return sky_blocks_of(s, out);
 }
+int rt_debug_beam_lists(rt_dev_scene *s, uint64_t totals[8], uint32_t *n_out, float *cut_out, uint64_t *entries_out,
+                        uint32_t cap_lists) {
+    if (!s || !totals || s->kind == 3) return RT_E_ARG;
+    std::memset(totals, 0, 8 * sizeof(uint64_t));
+    char name[64] = {0};
+    if (rt_debug_launches(s, name, int(sizeof(name))) < 0) return RT_E_ARG;  // resolves the fold order (synchronises)
+    const LastRender &L = s->last;
+    if (!L.beam_lists || !L.beam_cap || std::strncmp(name, "k_inw_pm", 8) != 0) return RT_OK;
+    const size_t lists = L.beam_lists, cap = L.beam_cap, esz = L.beam16 ? sizeof(uint32_t) : sizeof(uint2);
+    if ((n_out || cut_out || entries_out) && cap_lists < lists) return RT_E_ARG;
+    if (s->fold.beam_n.bytes < lists * 8 || s->fold.beam.bytes < lists * cap * esz) return RT_E_ARG;
+    try {
+        HIP_OK(hipSetDevice(s->device));
+        HIP_OK(hipDeviceSynchronize());
+        std::vector<uint32_t> nc(lists * 2);  // the counts, then the cuts
+        HIP_OK(hipMemcpy(nc.data(), s->fold.beam_n.p, lists * 8, hipMemcpyDeviceToHost));
+        std::vector<uint32_t> raw;
+        if (entries_out) {
+            raw.resize(lists * cap * esz / sizeof(uint32_t));
+            HIP_OK(hipMemcpy(raw.data(), s->fold.beam.p, lists * cap * esz, hipMemcpyDeviceToHost));
+            std::memset(entries_out, 0, lists * cap * sizeof(uint64_t));
+        }
+        uint64_t nonempty = 0, entries = 0, cuts = 0, offs = 0;
+        for (size_t l = 0; l < lists; l++) {
+            const uint32_t nw = nc[l];
+            const bool off = nw == rtk::kBeamOff;
+            const uint32_t cnt = off ? 0u : (nw & 0xffu);
+            float cut;
+            std::memcpy(&cut, &nc[lists + l], sizeof(cut));
+            if (n_out) n_out[l] = off ? rtk::kBeamOff : cnt;
+            if (cut_out) cut_out[l] = cut;
+            offs += off;
+            nonempty += cnt > 0;
+            entries += cnt;
+            cuts += !off && std::isfinite(cut);  // +inf: every leaf that passed the tests is listed
+            if (!entries_out || cnt == 0) continue;
+            // the block's 64 lists share its region of 64 * cap entries (k_inw_beam)
+            const size_t base = (l & ~size_t(63)) * cap + (nw >> 8);
+            if (cnt > cap || base + cnt > lists * cap) return RT_E_ARG;
+            for (uint32_t j = 0; j < cnt; j++) {
+                uint64_t id, key;
+                if (L.beam16) { const uint32_t e = raw[base + j]; id = e & 0xffffu; key = e & 0xffff0000u; }
+                else { id = raw[2 * (base + j)]; key = raw[2 * (base + j) + 1]; }
+                entries_out[l * cap + j] = id | (key << 32);
+            }
+        }
+        const uint64_t v[8] = {lists, nonempty, entries, cuts, offs, cap, 0, 0};
+        std::memcpy(totals, v, sizeof(v));
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_beam_keep_host(const float cam_pos[3], const float cd[3], float aperture, float focus, float sf_max,
+                      float wbound, const float box[6], const float *sph, uint32_t bin, uint32_t bins, int prune,
+                      int *candidate) {
+    if (!cam_pos || !cd || !box || prune < 0 || prune > 2 || bin >= std::max(1u, bins)) return RT_E_ARG;
+    rtk::BeamGeom g;
+    if (!rtk::beam_geom(cam_pos, aperture, focus, sf_max, wbound, g)) return RT_E_UNSUPPORTED;
+    const rtk::BeamPrune P = rtk::beam_prune_of(g, prune, bins);
+    // k_inw_beam's central ray: from co + cd along cd, the reciprocals correctly rounded
+    const float o[3] = {cam_pos[0] + cd[0], cam_pos[1] + cd[1], cam_pos[2] + cd[2]};
+    const float id[3] = {1.0f / cd[0], 1.0f / cd[1], 1.0f / cd[2]};
+    if (candidate) *candidate = 0;
+    if (!(std::isfinite(id[0]) && std::isfinite(id[1]) && std::isfinite(id[2]))) return 0;  // the list is switched off
+    const bool neg[3] = {cd[0] < 0.0f, cd[1] < 0.0f, cd[2] < 0.0f};
+    float nr[3], fr[3], te, tx;
+    for (int a = 0; a < 3; a++) { nr[a] = neg[a] ? box[3 + a] : box[a]; fr[a] = neg[a] ? box[a] : box[3 + a]; }
+    rtk::beam_slab(nr, fr, o, id, neg, P.R, te, tx);
+    if (!(std::fmax(te, P.tmin) <= std::fmin(tx, P.tfar))) return 0;
+    if (candidate) *candidate = 1;
+    if (P.mode == 0) return 1;
+    if (!rtk::beam_box_keep(P, nr, fr, o, id, neg, te, tx)) return 0;
+    if (P.mode >= 2 && sph && !rtk::beam_sphere_keep(P, o, cd, sph, sph + 4, bin)) return 0;
+    return 1;
+}
+
 int rt_debug_chunks(rt_dev_scene *s) {
     if (!s) return RT_E_ARG;
     return s->last.chunks;

@@ -134,6 +134,9 @@ struct LastRender {
     uint32_t ring[2] = {0, 0}; // ... its fold windows (pixel-major, sample-major)
     bool sky = false;          // ... it ran the sky-block kernels (rt_debug_sky_blocks)
     uint32_t sky_blocks = 0;   // ... the frame's 8x8 blocks
+    uint32_t beam_lists = 0;   // ... its beam lists, units x time bins (0: none; rt_debug_beam_lists)
+    uint32_t beam_cap = 0;     // ... entries a list can hold
+    bool beam16 = false;       // ... entries of 32 bits (InwScene::beam16)
 };
 
 // A prepared scene: device-resident records, LBVH nodes, lights and sample tables.

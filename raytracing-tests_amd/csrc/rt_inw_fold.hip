@@ -75,8 +75,14 @@ __device__ __forceinline__ bool inw_sample_major(const uint32_t *mode, uint32_t 
 // One lane per pixel unit walks the culling BVH with that ray against the boxes inflated by
 // beam_R and keeps the beam_cap leaves of smallest entry t, sorted; beam_cut is the smallest
 // entry t of a leaf it could not keep.
+// bp (rt_options.inw_beam_prune, rt_beam_prune.hpp): a child that passes that test is tested again
+// with the beam's radius over its own depth interval (bp.mode >= 1), and a leaf of a sphere scene
+// against the segment its centre sweeps in the list's time bin (bp.mode = 2).  A leaf that fails
+// can be touched by no primary ray of the pixel: it is neither listed nor counted in the cut.  The
+// key of a listed leaf stays the entry into the box inflated by beam_R.
 constexpr int kBeamBlock = 128, kBeamStack = 48, kBeamCapMax = 32;
-__global__ __launch_bounds__(kBeamBlock) void k_inw_beam(Frame f, InwScene S, const uint32_t *mode, uint32_t force) {
+__global__ __launch_bounds__(kBeamBlock) void k_inw_beam(Frame f, InwScene S, const uint32_t *mode, uint32_t force,
+                                                         BeamPrune bp) {
     if (inw_sample_major(mode, force)) return;
     __shared__ int st[kBeamStack * kBeamBlock];
     __shared__ uint2 lst[kBeamCapMax * kBeamBlock];
@@ -100,6 +106,8 @@ __global__ __launch_bounds__(kBeamBlock) void k_inw_beam(Frame f, InwScene S, co
         // near / far planes of each axis for this direction, inflated outward by R
         const uint32_t ox = cd.x < 0.0f ? 3u : 0u, oy = cd.y < 0.0f ? 4u : 1u, oz = cd.z < 0.0f ? 5u : 2u;
         const f3 rn = f3{cd.x < 0.0f ? R : -R, cd.y < 0.0f ? R : -R, cd.z < 0.0f ? R : -R};
+        const float oa[3] = {o.x, o.y, o.z}, ida[3] = {id.x, id.y, id.z}, cda[3] = {cd.x, cd.y, cd.z};
+        const bool neg[3] = {cd.x < 0.0f, cd.y < 0.0f, cd.z < 0.0f};
         int *stk = st + threadIdx.x;
         int sp = 0, cur = S.beam_bins > 1u ? (int)(1u + S.wbin_base + blockIdx.y * S.wbin_stride) : S.wroot;
         while (!off) {
@@ -118,6 +126,15 @@ __global__ __launch_bounds__(kBeamBlock) void k_inw_beam(Frame f, InwScene S, co
                                        ((fza[k] - rn.z) - o.z) * id.z);
                 if (!(fmaxf(te, t0) <= fminf(tx, t1))) continue;
                 const int l = lka[k];
+                if (bp.mode) {
+                    const float nr[3] = {nxa[k], nya[k], nza[k]}, fr[3] = {fxa[k], fya[k], fza[k]};
+                    if (!beam_box_keep(bp, nr, fr, oa, ida, neg, te, tx)) continue;
+                    if (l <= 0 && bp.mode >= 2u && S.sph) {
+                        const float4 p = S.sph[3 * (uint32_t)(-l)], q = S.sph[3 * (uint32_t)(-l) + 1];
+                        const float pa[4] = {p.x, p.y, p.z, p.w}, qa[3] = {q.x, q.y, q.z};
+                        if (!beam_sphere_keep(bp, oa, cda, pa, qa, S.beam_bins > 1u ? blockIdx.y : 0u)) continue;
+                    }
+                }
                 if (l > 0) {
                     if (sp == kBeamStack) off = true;
                     else stk[(sp++) * kBeamBlock] = l;
@@ -966,10 +983,11 @@ int inw_fold_blocks_per_cu(RenderKernel k) {
     default: return occupancy_of(k_inw_pm<false>, kBlock);
     }
 }
-hipError_t launch_inw_beam(const Frame &f, const InwScene &sc, const uint32_t *mode, uint32_t force, hipStream_t s) {
+hipError_t launch_inw_beam(const Frame &f, const InwScene &sc, const BeamPrune &bp, const uint32_t *mode, uint32_t force,
+                           hipStream_t s) {
     const uint32_t n = units_of(f);
     const uint32_t nb = sc.beam_bins > 1u ? sc.beam_bins : 1u;
-    hipLaunchKernelGGL(k_inw_beam, dim3((n + kBeamBlock - 1) / kBeamBlock, nb), dim3(kBeamBlock), 0, s, f, sc, mode, force);
+    hipLaunchKernelGGL(k_inw_beam, dim3((n + kBeamBlock - 1) / kBeamBlock, nb), dim3(kBeamBlock), 0, s, f, sc, mode, force, bp);
     return hipGetLastError();
 }
 size_t inw_cost_uints(uint32_t nblk) { return 3 * size_t(nblk) + 256 + kSkyInfo; }
@@ -983,7 +1001,7 @@ size_t inw_sky_info_at(uint32_t nblk) { return 2 * size_t(nblk) + 256; }
 // past them.
 hipError_t launch_inw_fold(const Frame &f, const InwScene &sc, float4 *ring, uint32_t ring_pm, uint32_t ring_sm,
                            unsigned *counter, uint32_t *mode, uint32_t force, int blocks, int blocks_ln,
-                           uint32_t *cost, bool sky, hipStream_t s) {
+                           uint32_t *cost, bool sky, const BeamPrune &bp, hipStream_t s) {
     for (uint32_t r : {ring_pm, ring_sm})
         if (r < 64 || (r & (r - 1))) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(mode, 0, 2 * sizeof(uint32_t), s);
@@ -1009,7 +1027,7 @@ hipError_t launch_inw_fold(const Frame &f, const InwScene &sc, float4 *ring, uin
         if ((e = hipMemsetAsync(hist, 0, (256 + kSkyInfo) * sizeof(uint32_t), s)) != hipSuccess) return e;
         const dim3 g((nblk + 3u) / 4u);  // 4 blocks of 8x8 pixels per 256-lane block
         if (sky) {
-            if ((e = launch_inw_beam(f, sc, mode, force, s)) != hipSuccess) return e;
+            if ((e = launch_inw_beam(f, sc, bp, mode, force, s)) != hipSuccess) return e;
             hipLaunchKernelGGL(k_inw_sky_classify, g, dim3(kBlock), 0, s, f, sc, flag, hist + 256, mode, force);
             hipLaunchKernelGGL(k_inw_sky, dim3(nblk), dim3(kSkyBlock), 0, s, f, sc, flag, hist + 256);
         }
@@ -1022,7 +1040,7 @@ hipError_t launch_inw_fold(const Frame &f, const InwScene &sc, float4 *ring, uin
         if ((e = hipGetLastError()) != hipSuccess) return e;
         border = ord;
     }
-    if (sc.beam && !sky && (e = launch_inw_beam(f, sc, mode, force, s)) != hipSuccess) return e;
+    if (sc.beam && !sky && (e = launch_inw_beam(f, sc, bp, mode, force, s)) != hipSuccess) return e;
     for (int k = 0; k < 2; k++) {  // (pm, then sm) each with its own queue counter
         if ((e = hipMemsetAsync(counter + 16 * k, 0, sizeof(unsigned), s)) != hipSuccess) return e;
         if (k == 0 && sc.xcdq && (e = hipMemsetAsync(counter + 64, 0, 8 * 16 * sizeof(unsigned), s)) != hipSuccess)

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_beam_prune.hpp"
+
 namespace rtk {
 
 // Per-launch uniforms, computed on the host exactly as the reference host + shader
@@ -412,13 +414,15 @@ hipError_t launch_iow03_resolve(const Frame &f, const SpecRecs &R, bool final_pa
 // staged in LDS (ring: max(blocks * 4, blocks_ln * 12) waves)
 hipError_t launch_inw_fold(const Frame &f, const InwScene &sc, float4 *ring, uint32_t ring_pm, uint32_t ring_sm,
                            unsigned *counter, uint32_t *mode, uint32_t force, int blocks, int blocks_ln,
-                           uint32_t *cost, bool sky, hipStream_t s);
+                           uint32_t *cost, bool sky, const BeamPrune &bp, hipStream_t s);
 // cost: the claim order's workspace, inw_cost_uints(blocks of 8x8 units) uints; its sky-block
 // bookkeeping (rt_debug_sky_blocks) starts at inw_sky_info_at(blocks): flagged, rendered at + 1, + 2
 size_t inw_cost_uints(uint32_t nblk);
 size_t inw_sky_info_at(uint32_t nblk);
-// the pixel beams of a pixel-major frame (sc.beam*; exits when the probe picks sample-major)
-hipError_t launch_inw_beam(const Frame &f, const InwScene &sc, const uint32_t *mode, uint32_t force, hipStream_t s);
+// the pixel beams of a pixel-major frame (sc.beam*; exits when the probe picks sample-major); bp:
+// which leaves the lists drop (rt_beam_prune.hpp)
+hipError_t launch_inw_beam(const Frame &f, const InwScene &sc, const BeamPrune &bp, const uint32_t *mode, uint32_t force,
+                           hipStream_t s);
 // rt_trace.hip: n_rays closest-hit queries (rt_ray / rt_hit as 2 float4 each) on a persistent grid
 // of at most cus * inw_trace_blocks_per_cu blocks; queue: one u32 (zeroed here); counters: 6 x u64
 // added to (slots 0, 1, 2, 4), or null.  sc.fused picks the fused-cull instance.

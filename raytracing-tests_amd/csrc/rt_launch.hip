@@ -88,24 +88,18 @@ std::vector<std::pair<int, int>> chunk_plan(int spp, bool lpt) {
 // parameter range [tmin, tfar] that covers the scene, every primary ray lies within
 // R = delta0 * max |1 - t / L| (+ rounding slack) of the central ray.  A sample ray's hit at t
 // has central parameter <= t * kappa, kappa = L / (L - delta0).
-int set_beam(rt_dev_scene *s, const rtk::Frame &f, rtk::InwScene &sc) {
+// bp: what k_inw_beam drops from the lists (rt_options.inw_beam_prune; rt_beam_prune.hpp).
+int set_beam(rt_dev_scene *s, const rtk::Frame &f, rtk::InwScene &sc, rtk::BeamPrune &bp) {
     const uint32_t cap = 32;
     const InwWalk &w = s->walk;
     DevBuf &beam = s->fold.beam, &beam_n = s->fold.beam_n;
     const double units = double(rtk::units_of(f));
-    const double ap = std::fabs(double(f.aperture)), L = double(f.focus) - 1.0;
-    const double d0 = 0.5 * ap * double(s->sf_max) * (1.0 + 1e-4) + 1e-6;
-    if (!s->opt.inw_beams || !sc.wnodes || f.n_focus > 0 || !(L > 8.0 * d0 + 1e-3) ||
-        units * cap * 8.0 * std::max<uint32_t>(1u, w.wbins) > 8.0e9)  // list capacity; each list is packed
+    rtk::BeamGeom g;
+    if (!s->opt.inw_beams || !sc.wnodes || f.n_focus > 0 ||
+        units * cap * 8.0 * std::max<uint32_t>(1u, w.wbins) > 8.0e9 ||  // list capacity; each list is packed
+        !rtk::beam_geom(f.pos, f.aperture, f.focus, s->sf_max, w.wbound, g))
         return RT_OK;
-    const double cam = std::sqrt(double(f.pos[0]) * f.pos[0] + double(f.pos[1]) * f.pos[1] + double(f.pos[2]) * f.pos[2]);
-    const double Lh = L + 1e-3 * (1.0 + cam), Ll = L - 1e-3 * (1.0 + cam);
-    if (!(Ll > 4.0 * d0)) return RT_OK;
-    // every point of a culling box lies within sqrt(3) * wbound of the origin
-    const double tfar = (cam + 1.0 + std::sqrt(3.0) * double(w.wbound) + 2.0) / (1.0 - d0 / Ll) * 1.001;
-    const double tmin = -Lh / (Ll - d0) - 0.01;
-    const double r = d0 * std::fmax(1.0 - tmin / Ll, std::fabs(1.0 - tfar / Ll));
-    const double R = r + 2e-3 + 1e-5 * (cam + tfar);
+    const double R = g.R, tmin = g.tmin, tfar = g.tfar;
     // object ids below 2^16: one uint32 per entry (the id, t's high half), else (id, t)
     const bool b16 = s->n <= 65536u && s->opt.inw_beams != 2;  // inw_beams = 2: the pairs (A/B)
     // one list per unit and time bin when the scene has time-bin trees (rt_options.inw_time_bins)
@@ -130,7 +124,8 @@ int set_beam(rt_dev_scene *s, const rtk::Frame &f, rtk::InwScene &sc) {
     sc.beam_R = float(R);
     sc.beam_tmin = float(tmin);
     sc.beam_tfar = float(tfar);
-    sc.beam_kappa = float(Lh / (Ll - d0) * (1.0 + 1e-5));
+    sc.beam_kappa = float(g.kappa);
+    bp = rtk::beam_prune_of(g, s->opt.inw_beam_prune, nb);
     return RT_OK;
 }
 
@@ -220,7 +215,8 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
         if (fold.cost.reserve(need) != hipSuccess) return RT_E_HIP;
         cost = fold.cost.as<uint32_t>();
     }
-    if (int rc = set_beam(s, f, sc); rc != RT_OK) return rc;
+    rtk::BeamPrune bp;
+    if (int rc = set_beam(s, f, sc, bp); rc != RT_OK) return rc;
     // sky blocks (inw_sky_blocks = 0: off): INW-01 frames with beam lists and the claim
     // order, the single-focus camera, a fresh sample's stack below the wide walk's condition, no
     // per-pixel ray count or occupancy hook; the pixel-major verdict is read on the device
@@ -243,6 +239,9 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
         last.fu = last.ln && sc.fused;
         last.sky = sky;
         last.sky_blocks = rtk::units_of(f) / 64;
+        last.beam_lists = sc.beam ? sc.beam_units * (sc.beam_bins > 1u ? sc.beam_bins : 1u) : 0u;
+        last.beam_cap = sc.beam_cap;
+        last.beam16 = sc.beam16 != 0;
         rt_path_info &P = last.path;
         P.launches = 1;
         P.order_forced = force != 0;
@@ -264,6 +263,7 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
         P.time_bins = sc.wnodes && !sc.gstk ? int(sc.wbins) : 0;  // the GQ walks read the staged (swept) tree
         P.beam_bins = sc.beam ? int(sc.beam_bins) : 0;
         P.sphere_records = sc.sph ? 1 : 0;
+        P.beam_prune = sc.beam ? int(bp.mode >= 2u && !sc.sph ? 1u : bp.mode) : 0;  // step 2 needs the sphere records
         s->last = last;
     }
     if (epoch == 0) e = hipMemsetAsync(fold.ring.p, 0xff, fold.ring.bytes, st);
@@ -271,7 +271,7 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     if (e == hipSuccess && ev) e = hipEventRecord(ev->first, st);
     if (e == hipSuccess)
         e = rtk::launch_inw_fold(f, sc, fold.ring.as<float4>(), ring_pm, ring_sm, s->counter.as<unsigned>(),
-                                 fold.mode.as<uint32_t>(), force, blocks, blocks_ln, cost, sky, st);
+                                 fold.mode.as<uint32_t>(), force, blocks, blocks_ln, cost, sky, bp, st);
     if (e == hipSuccess && ev) e = hipEventRecord(ev->second, st);
     if (e != hipSuccess) {
         fold.ring_frame = 0;

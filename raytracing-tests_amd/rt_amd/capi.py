@@ -80,7 +80,8 @@ class RtOptions(C.Structure):
         "rounds_seq", "rounds_spec", "park_min",
         "spec_iters", "spec_probe", "spec_heavy", "spec_rounds", "spec_tail_rounds", "spec_tail_budget", "spec_scan",
         "spec_chain", "spec_alt", "spec_alt_cap", "spec_alt_seg", "spec_alt_every", "spec_spread", "spec_prior_from",
-        "spec_sort", "spec_solo", "spec_validate")] + [("spec_max_gb", C.c_double), ("inw_sky_blocks", C.c_int)]
+        "spec_sort", "spec_solo", "spec_validate")] + [("spec_max_gb", C.c_double), ("inw_sky_blocks", C.c_int),
+                                                    ("inw_beam_prune", C.c_int)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "size"}
@@ -93,7 +94,8 @@ class RtPathInfo(C.Structure):
                 ("lds_nodes", C.c_int), ("claim_order", C.c_int), ("ring_entries", C.c_int), ("iow_bvh", C.c_int),
                 ("ring_lds", C.c_int), ("stackless", C.c_int), ("lbvh_lds_nodes", C.c_int),
                 ("qnodes", C.c_int), ("global_stack", C.c_int), ("walk_stack", C.c_int), ("ref_walks", C.c_uint64),
-                ("time_bins", C.c_int), ("beam_bins", C.c_int), ("sphere_records", C.c_int)]
+                ("time_bins", C.c_int), ("beam_bins", C.c_int), ("sphere_records", C.c_int),
+                ("beam_prune", C.c_int)]
 
     ORDERS = {0: None, 1: "pixel-major", 2: "sample-major", 3: "per-pixel", 4: "sample-parallel", 5: "sequential"}
 
@@ -187,6 +189,9 @@ SIGNATURES = {
     "rt_debug_iow_dump": (C.c_int, [C.c_void_p, _U32P, _FP, _FP]),
     "rt_debug_path": (C.c_int, [C.c_void_p, C.POINTER(RtPathInfo)]),
     "rt_debug_sky_blocks": (C.c_int, [C.c_void_p, _U32P]),
+    "rt_debug_beam_lists": (C.c_int, [C.c_void_p, _U64P, _U32P, _FP, _U64P, C.c_uint32]),
+    "rt_beam_keep_host": (C.c_int, [_FP, _FP, C.c_float, C.c_float, C.c_float, C.c_float, _FP, _FP, C.c_uint32,
+                                    C.c_uint32, C.c_int, _IP]),
     "rt_debug_wide_info": (C.c_int, [C.c_void_p, _U32P, _U32P]),
     "rt_tile_deal": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _IP, C.c_int]),
     "rt_group_create": (C.c_void_p, [_IP, C.c_int]),
