@@ -569,7 +569,8 @@ __device__ __forceinline__ void inw_hit_normal(const InwScene &S, int bg, f3 o, 
 // a lane's state machine is selects on integers, so the compiler keeps no loop-carried lane mask
 // to re-merge after every region (DESIGN.md §5.2 "The walk trip").  A lane's state is `cur`: a
 // node (> 0), a leaf (<= 0: object -cur) or kWalkDone (it walks no more: its stack ran empty or
-// overflowed, or the walk's conditions never held for it).
+// overflowed, or the walk's conditions never held for it).  A node step whose nearest surviving
+// child is a leaf takes it in its own trip when the lane holds none (DESIGN.md §5.2 "Leaf takes").
 constexpr int kWalkDone = (-2147483647 - 1);
 template <bool WANT_NORMAL, bool LN = false, bool FU = false, bool QN = false, class KS = FStack, bool SP = true>
 __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float ratio, bool invert, float &tlim,
@@ -694,10 +695,13 @@ __device__ float inw_traverse_wide(const InwScene &S, KS &K, f3 o, f3 d, float r
         // query kernel at size 0, and GStack's cap is a constant.  With cap < 0 an idle lane would
         // count as overflowed and go to the reference walk: the same result, for more work)
         const bool over = p > cap;
-        // a leaf is taken (and the lane pops) unless the lane still holds one: then it waits on it
-        const bool take = cur <= 0 && cur != kWalkDone && pend < 0;
-        pend = take ? -cur : pend;
-        const bool pop = take || tn == kMiss;
+        // a leaf is taken (and the lane pops) unless the lane still holds one: then it waits on it.
+        // The leaf is the lane's own state or, in the node step's own trip, the step's nearest
+        // surviving child (nxt is either: a lane not on a node has nxt = cur and no miss)
+        const bool miss = tn == kMiss;
+        const bool take = nxt <= 0 && nxt != kWalkDone && !miss && pend < 0;
+        pend = take ? -nxt : pend;
+        const bool pop = take || miss;
         // every lane reads the entry under its top (its own column: q <= cap + 2, the spare slots;
         // at p <= 0 a value nobody uses)
         const int q = max(p - 1, 0);
