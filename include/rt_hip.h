@@ -103,7 +103,8 @@ typedef struct rt_stats {
 typedef struct rt_options {
     uint32_t size;          /* sizeof(rt_options), set by rt_options_default; checked by the setters */
     /* INW (In-Next-Week 01 / 04) */
-    int inw_wide_walk;      /* [build] 1: 4-wide culling walk with the reference's leaf tests; 0: the LBVH walk as the shader does it */
+    int inw_wide_walk;      /* [build] 1: 4-wide culling walk with the reference's leaf tests; 0: the LBVH walk as the shader does it
+                             * (also taken, per scene, when an object sticks out of its caller-supplied leaf box: DESIGN.md §2) */
     int inw_order;          /* fold kernel: 0 = the probe picks, 1 = pixel-major, 2 = sample-major, -1 = per-pixel k_inw */
     int inw_beams;          /* per-pixel candidate lists for primary rays (pixel-major frames); 1: entries of
                                32 bits (16-bit object id, entry t rounded down) when ids fit, 2: (id, t) pairs */

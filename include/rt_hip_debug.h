@@ -151,6 +151,12 @@ int rt_debug_time_bins(const float *nodes, const float *geom, uint32_t n, uint32
                        uint32_t wnodes_cap, uint32_t info[4]);
 int rt_debug_bin_boxes(const float *geom, uint32_t n, uint32_t bins, uint32_t b, float *boxes_out);
 int rt_debug_sphere_records(const float *geom, uint32_t n, int layout, float *out);
+/* Objects inside their leaf boxes: how far, at most, an object of the GeometryBuff
+ * records sticks out of its box over the shutter interval, as a multiple of the margin up to which
+ * a scene takes the wide walk (1e-5 * max(1, largest |coordinate| of the box)); > 1: the scene is
+ * built as with inw_wide_walk = 0.  The boxes are the leaves of `nodes` ((2n - 1) x 8), or with
+ * nodes = NULL the rows of aabbs (n x 6).  *worst_out is +inf for a value that is not finite. */
+int rt_debug_inw_stick_out(const float *geom, uint32_t n, const float *nodes, const float *aabbs, double *worst_out);
 /* Read-back hooks for the culling and bookkeeping structures (tests/test_walk_structs.py,
  * tests/test_gpu_walk_structs.py check each one directly against DESIGN.md §2's "every structure is
  * conservative").  None of them changes what a render path builds or reads.

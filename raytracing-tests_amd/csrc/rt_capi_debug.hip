@@ -370,6 +370,12 @@ int rt_debug_sphere_records(const float *geom, uint32_t n, int layout, float *ou
     return 1;
 }
 
+int rt_debug_inw_stick_out(const float *geom, uint32_t n, const float *nodes, const float *aabbs, double *worst_out) {
+    if (!geom || n == 0 || (!nodes && !aabbs) || !worst_out) return RT_E_ARG;
+    *worst_out = nodes ? rtamd::inw_stick_out(geom, n, nodes, 0) : rtamd::inw_stick_out(geom, n, aabbs, 6);
+    return RT_OK;
+}
+
 int rt_debug_walk_dump(rt_dev_scene *s, int what, void *out, size_t cap_bytes, uint64_t info[8]) {
     if (!s || s->kind == 3 || s->broken || !info) return RT_E_ARG;
     HIP_OK(hipSetDevice(s->device));

@@ -822,6 +822,52 @@ bool inw_wide_build(const float *nodes, uint32_t n, InwWide &out) {
     return true;
 }
 
+// Objects inside their leaf boxes (rt_host.hpp).  The wide walk culls a subtree whose
+// box entry lies past its best hit, and its leaf-entry guard and the beam lists' stop rule order
+// candidates by box entry: all of it assumes a hit does not lie in front of its own leaf box by
+// more than rounding.  The packers' boxes satisfy that (objects stick out by a few ulps); boxes a
+// caller supplies need not, and the reference culls with whatever it is given.  The margin is the
+// rounding term of the culling boxes' own inflation (big * 1e-5, inw_wide_build), so an object
+// within it still lies inside its culling box.
+double inw_stick_out(const float *geom, uint32_t n, const float *boxes, uint32_t stride) {
+    double worst = 0.0;
+    auto one = [&](uint32_t g, const float *b) {
+        const float *f = geom + size_t(g) * 28;
+        const bool cuboid = int(f[18] + 0.1f) == 2;
+        double big = 1.0;
+        for (int k = 0; k < 6; k++) big = std::fmax(big, std::fabs(double(b[k])));
+        const double margin = double(kInwStickOut) * big;
+        for (int a = 0; a < 3; a++) {
+            double e = 0.0;
+            for (int c = 0; c < 3; c++) {
+                const double x = double(f[3 + 3 * c + a]) * double(f[12 + c]);
+                e += cuboid ? 0.5 * std::fabs(x) : x * x;
+            }
+            if (!cuboid) e = std::sqrt(e);
+            const double c1 = double(f[a]), c0 = c1 - double(f[15 + a]);
+            const double out = std::fmax(double(b[a]) - (std::fmin(c0, c1) - e), (std::fmax(c0, c1) + e) - double(b[3 + a]));
+            // (fmin / fmax drop a NaN operand: test the operands; an infinite box face holds everything)
+            if (!std::isfinite(c0) || !std::isfinite(c1) || !std::isfinite(e) || std::isnan(b[a]) || std::isnan(b[3 + a]) ||
+                std::isnan(out)) {
+                worst = INFINITY;
+                return;
+            }
+            worst = std::fmax(worst, out / margin);
+        }
+    };
+    if (stride) {
+        for (uint32_t g = 0; g < n; g++) one(g, boxes + size_t(g) * stride);
+    } else {
+        for (uint32_t i = 0; i < 2 * n - 1; i++) {
+            const float *nd = boxes + size_t(i) * 8;
+            if (nd[6] > 0.1f) continue;  // an internal node
+            const float id = -nd[6];
+            if (id >= 0.0f && id < float(n)) one(uint32_t(id), nd);
+        }
+    }
+    return worst;
+}
+
 // Time-bin trees.  Object g's centre at time ratio r is p - delta (1 - r) (the kernels' object
 // offset (o - p) + delta (1 - r), 01_BVH...glsl), so over [r0, r1] it sweeps the segment between
 // its centres at r0 and r1; its box there is that segment's box widened by the object's own half

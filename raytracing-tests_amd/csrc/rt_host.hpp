@@ -145,6 +145,16 @@ bool inw_wide_add_bins(const float *geom, uint32_t n, uint32_t bins, InwWide &w)
 // The culling boxes of bin b of `bins` (6 floats per object: lo xyz, hi xyz), rounded outward; the
 // largest |coordinate| goes into wbound (max).  false: a record's extent is not finite.
 bool inw_bin_boxes(const float *geom, uint32_t n, uint32_t bins, uint32_t b, std::vector<float> &boxes, float &wbound);
+// Objects inside their leaf boxes: how far, at most, an object sticks out of its box
+// over the shutter interval, as a multiple of the box's margin kInwStickOut * max(1, largest
+// |coordinate| of the box).  The object's extent is its centre's sweep p - delta .. p widened per world
+// axis a by the ellipsoid's sqrt(sum_c (R_ac s_c)^2) or the cuboid's rotated corners
+// sum_c |R_ac| s_c / 2, with R's columns floats 3..5, 6..8, 9..11 (the reference's placement).  Object
+// g's box is boxes[g * stride .. + 6] (lo xyz, hi xyz): the caller's aabbs (stride 6), or with
+// stride 0 `boxes` is an LBVH node buffer ((2n - 1) x 8) and the box is the object's leaf node.
+// Returns +inf for a value that is not finite; the wide walk applies while the result is <= 1.
+constexpr float kInwStickOut = 1e-5f;
+double inw_stick_out(const float *geom, uint32_t n, const float *boxes, uint32_t stride);
 // The reference walk's stack high-water mark over both child orders (high; its pushes can only
 // drop while size + high > 40) and whether the node buffer has the layout the stackless LBVH walks
 // rely on (stackless: every internal node's children at L (odd), L + 1 with rightData = the node,

@@ -86,6 +86,14 @@ int upload_textures(rt_dev_scene *s, const rt_texture *tex, int n_tex) {
     return RT_OK;
 }
 
+// Whether a scene takes the wide walk: rt_options.inw_wide_walk, and every object inside its leaf box
+// up to the margin of rtamd::inw_stick_out (DESIGN.md §2 "Objects inside their leaf boxes").  A scene
+// with caller boxes that an object sticks out of is built as with inw_wide_walk = 0: the reference's
+// LBVH walks, no beam lists, no RI grid.  boxes / stride as inw_stick_out takes them.
+bool inw_wide_ok(const rt_dev_scene *s, const float *geom, uint32_t n, const float *boxes, uint32_t stride) {
+    return s->opt.inw_wide_walk && n >= 2 && rtamd::inw_stick_out(geom, n, boxes, stride) <= 1.0;
+}
+
 // The quantised culling BVH (DESIGN.md §5.2 "Quantised nodes") from the scene's wide nodes, on the
 // device: planes rounded outward by kQMargin beyond the wide nodes' own (the error bound of the
 // walk's decode is below it while every coordinate lies within 1000 of the origin, the fused
@@ -107,7 +115,9 @@ int make_qnodes(InwWalk &w) {
 // rtamd::ri_grid_build) and uploaded.
 // ms (may be null): host time of the builds, then of the uploads
 // geom (may be null): the reference's GeometryBuff records, for the time-bin trees
-int make_inw_wide(rt_dev_scene *s, const float *nodes, uint32_t n, double *ms = nullptr, const float *geom = nullptr) {
+// wide: the scene takes the wide walk (inw_wide_ok)
+int make_inw_wide(rt_dev_scene *s, const float *nodes, uint32_t n, bool wide, double *ms = nullptr,
+                  const float *geom = nullptr) {
     InwWalk &d = s->walk;
     d.reset();
     const auto t0 = std::chrono::steady_clock::now();
@@ -116,7 +126,7 @@ int make_inw_wide(rt_dev_scene *s, const float *nodes, uint32_t n, double *ms = 
     const bool walkable = rtamd::lbvh_walk_info(nodes, n, high, sl);
     rtamd::InwWide w;
     rtamd::RiGrid g;
-    const bool ok = walkable && s->opt.inw_wide_walk && rtamd::inw_wide_build(nodes, n, w);
+    const bool ok = walkable && wide && rtamd::inw_wide_build(nodes, n, w);
     if (ok) g = rtamd::ri_grid_build(w.leafbox.data(), n);
     if (ok && geom && s->opt.inw_time_bins > 1) rtamd::inw_wide_add_bins(geom, n, uint32_t(s->opt.inw_time_bins), w);
     const auto t1 = std::chrono::steady_clock::now();
@@ -152,7 +162,7 @@ int make_inw_wide(rt_dev_scene *s, const float *nodes, uint32_t n, double *ms = 
 // The same structures built on the device from the scene's device LBVH (rt_build.hip, DESIGN.md
 // "Device build"; rt_options.inw_device_build): no host build, no upload.  ms: host wall time of
 // the build (its level loop and the RI grid read counts back) in ms[0], 0 in ms[1].
-int make_inw_wide_device(rt_dev_scene *s, uint32_t n, double *ms) {
+int make_inw_wide_device(rt_dev_scene *s, uint32_t n, bool wide, double *ms) {
     InwWalk &d = s->walk;
     d.reset();
     const auto t0 = std::chrono::steady_clock::now();
@@ -168,7 +178,7 @@ int make_inw_wide_device(rt_dev_scene *s, uint32_t n, double *ms) {
         if (be == hipErrorNotSupported) return RT_E_UNSUPPORTED;  // deeper than its level cap: the caller builds on the host
         HIP_OK(be);
     }
-    if (s->opt.inw_wide_walk) {
+    if (wide) {
         double dlo[3], dhi[3], inv[3];
         int dim[3];
         for (int a = 0; a < 3; a++) { dlo[a] = out.ri_lo[a]; dhi[a] = out.ri_hi[a]; }
@@ -442,7 +452,7 @@ int make_inw(rt_dev_scene *s, const float *geom, uint32_t n, int layout, const f
         if (s->sph_ok) HIP_OK(s->sph.store(sph.data(), sph.size() * sizeof(float)));
     }
     HIP_OK(s->nodes.store(nodes, size_t(2 * n - 1) * 8 * sizeof(float)));
-    if (int rc = make_inw_wide(s, nodes, n, nullptr, geom); rc != RT_OK) return rc;
+    if (int rc = make_inw_wide(s, nodes, n, inw_wide_ok(s, geom, n, nodes, 0), nullptr, geom); rc != RT_OK) return rc;
     if (s->n_lights) HIP_OK(s->lights.store(lights, size_t(s->n_lights) * 7 * sizeof(float)));
     else HIP_OK(s->lights.store(nullptr, 0));
     set_residency(s);
@@ -466,6 +476,7 @@ int update_inw(rt_dev_scene *s, const float *geom, uint32_t n, const float *node
     // the wide walk's structures and the RI grid built on the device from the device LBVH
     // (rt_options.inw_device_build; a caller's host LBVH keeps the host builders)
     const bool device_build = s->opt.inw_device_build && !nodes && n >= 2;
+    const float *const caller_nodes = nodes;
     // Until every step below has succeeded the buffers may hold a mix of the old and the new
     // scene (sizes included): the scene refuses renders (launch_scene) and keeps its old n and
     // counts, so nothing indexes past a buffer.  The new sizes are committed at the end.
@@ -506,8 +517,10 @@ int update_inw(rt_dev_scene *s, const float *geom, uint32_t n, const float *node
     }
     lap(1);
     double w[2] = {0.0, 0.0};
+    // (the leaf boxes: the caller's nodes', or with nodes = NULL the caller's boxes themselves)
+    const bool wide = caller_nodes ? inw_wide_ok(s, geom, n, caller_nodes, 0) : inw_wide_ok(s, geom, n, aabbs, 6);
     if (device_build) {
-        int rc = make_inw_wide_device(s, n, w);
+        int rc = make_inw_wide_device(s, n, wide, w);
         d.wbuild = 1;
         if (rc == RT_E_UNSUPPORTED) {
             // the binned SAH tree ran past the device build's level cap (a chain-like scene: a split
@@ -515,12 +528,12 @@ int update_inw(rt_dev_scene *s, const float *geom, uint32_t n, const float *node
             // device LBVH back and build the walk structures there, as rt_dev_scene_inw does
             host_nodes.resize(nbytes / sizeof(float));
             HIP_OK(hipMemcpy(host_nodes.data(), s->nodes.p, nbytes, hipMemcpyDeviceToHost));
-            rc = make_inw_wide(s, host_nodes.data(), n, w, geom);
+            rc = make_inw_wide(s, host_nodes.data(), n, wide, w, geom);
             d.wbuild = 2;
         }
         if (rc != RT_OK) return rc;
     } else {
-        if (int rc = make_inw_wide(s, nodes, n, w, geom); rc != RT_OK) return rc;
+        if (int rc = make_inw_wide(s, nodes, n, wide, w, geom); rc != RT_OK) return rc;
         d.wbuild = 0;
     }
     if (ms) { ms[2] = w[0]; ms[3] = w[1]; }

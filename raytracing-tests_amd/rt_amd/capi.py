@@ -199,6 +199,7 @@ SIGNATURES = {
     "rt_debug_time_bins": (C.c_int, [_FP, _FP, C.c_uint32, C.c_uint32, _FP, C.c_uint32, _U32P]),
     "rt_debug_bin_boxes": (C.c_int, [_FP, C.c_uint32, C.c_uint32, C.c_uint32, _FP]),
     "rt_debug_sphere_records": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP]),
+    "rt_debug_inw_stick_out": (C.c_int, [_FP, C.c_uint32, _FP, _FP, C.POINTER(C.c_double)]),
     "rt_debug_walk_dump": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, _U64P]),
     "rt_debug_inw_host_dump": (C.c_int, [_FP, C.c_uint32, _U32P, _FP, _FP, _U32P, _U32P, _U32P, _FP, _IP]),
     "rt_debug_iow_host_dump": (C.c_int, [_FP, _FP, C.c_uint32, _U32P, _FP, _FP]),
@@ -656,6 +657,18 @@ def walk_dump_all(scene) -> dict:
             "ri_lo": frame[0:3] if ok else None, "ri_hi": frame[3:6] if ok else None,
             "ri_inv": frame[6:9] if ok else None, "ri_dim": frame[9:12].view(np.int32) if ok else None,
             "wide_info": [int(x) for x in wi]}
+
+
+def inw_stick_out(geom: np.ndarray, nodes: np.ndarray | None = None, aabbs: np.ndarray | None = None) -> float:
+    """rt_debug_inw_stick_out: the most an object sticks out of its leaf box (of `nodes`, or of aabbs), as a
+    multiple of the margin up to which a scene takes the wide walk."""
+    geom = np.ascontiguousarray(geom, np.float32)
+    nodes = None if nodes is None else np.ascontiguousarray(nodes, np.float32)
+    aabbs = None if aabbs is None else np.ascontiguousarray(aabbs, np.float32)
+    out = C.c_double(0.0)
+    check(load().rt_debug_inw_stick_out(fptr(geom), len(geom), fptr(nodes), fptr(aabbs), C.byref(out)),
+          "rt_debug_inw_stick_out")
+    return out.value
 
 
 def lbvh_build(aabbs: np.ndarray) -> np.ndarray:

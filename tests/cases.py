@@ -85,6 +85,72 @@ def _dense_glass(n=160, **over):
     return sc
 
 
+MIXED_SEED = 8  # chosen so that tests/test_mixed_scenes.py's conditions hold for every mixed case
+
+
+def _mixed(preset, n, back=False, static=False, shrink=None, seed=MIXED_SEED, **over):
+    """n objects alternating ellipsoid and cuboid in a +-4 cube, each with three scales of its own
+    in 0.3..1.2 and three rotation angles in +-90 degrees, many of them moving by up to +-0.5 per
+    axis: the general 7-float4 records (no sphere records) with time bins, in frames.  INW-01: 60% of
+    the objects move; INW-04: those with index mod 5 below 3, and every 17th object is a light (object
+    0 is one, and moves).  Four materials in turn: absorbing, glass, mirror, mixed.  The camera looks
+    at the cube from (-7, 2.5, -7), or with back from the opposite corner, where dot(camera direction,
+    1) < 0 and the reference walk takes the other child order.  static: last_position = position.
+    shrink: the caller's boxes shrunk about their centres to that factor, and the LBVH over those, so
+    that objects stick out of their leaf boxes (the reference culls with whatever boxes it is given)."""
+    stage = R.PRESET_STAGE[preset]
+    _, _, cd, par = R.preset_desc(preset, 0, 1)
+    for k, v in over.items():
+        setattr(par, k, v)
+    sgn = -1.0 if back else 1.0
+    cd.position[0], cd.position[1], cd.position[2] = -7.0 * sgn, 2.5, -7.0 * sgn
+    cd.focus_dist = 8.0
+    if back:
+        cd.yaw_deg += 180.0
+    arr = (R.RtGeomDesc * n)()
+    rng = np.random.default_rng(seed)
+    for i in range(n):
+        d = arr[i]
+        d.type = R.RT_INW_ELLIPSOID if i % 2 == 0 else R.RT_INW_CUBOID
+        p, s, rot = rng.uniform(-4.0, 4.0, 3), rng.uniform(0.3, 1.2, 3), rng.uniform(-90.0, 90.0, 3)
+        mv, pick, col = rng.uniform(-0.5, 0.5, 3), rng.uniform(), rng.uniform(0.1, 0.9, 3)
+        moves = (i % 5 < 3) if stage == R.RT_STAGE_INW04 else pick < 0.6
+        if static or not moves:
+            mv = np.zeros(3)
+        for k in range(3):
+            d.position[k], d.last_position[k] = float(p[k]), float(p[k]) - float(mv[k])
+            d.scale[k], d.rotation_deg[k], d.color[k] = float(s[k]), float(rot[k]), float(col[k])
+        d.refractivity, d.reflectivity, d.scat_reflect, d.scat_refract = (
+            (0.0, 0.0, 0.0, 0.0), (0.65, 0.15, 0.0, 0.0), (0.0, 0.9, 0.0, 0.0), (0.3, 0.5, 0.2, 0.1))[i % 4]
+        d.refractive_index = 1.3 + 0.05 * (i % 8)
+        d.emissive = int(stage == R.RT_STAGE_INW04 and i % 17 == 0)
+    sc = R.Scene(stage=stage, desc=arr, n=n, camera=R.camera_from_desc(cd, stage), params=par)
+    for k, v in R.pack(arr, n, stage).items():
+        setattr(sc, k, v)
+    if shrink is not None:
+        sc.aabbs = shrink_boxes(sc.aabbs, shrink)
+        sc.nodes = R.lbvh_build(sc.aabbs)
+    return sc
+
+
+def shrink_boxes(aabbs, factor):
+    """The boxes (n, 6) shrunk about their centres to `factor` of their size, in float32."""
+    a = np.asarray(aabbs, np.float64)
+    mid, half = (a[:, 0:3] + a[:, 3:6]) / 2, (a[:, 3:6] - a[:, 0:3]) / 2 * factor
+    return np.ascontiguousarray(np.concatenate([mid - half, mid + half], axis=1), np.float32)
+
+
+def _mixed01(n=250, **kw):
+    return _mixed(R.PRESET_INW01_RANDOM, n, **{"width": 96, "height": 64, "spp": 6, "max_bounces": 10, **kw})
+
+
+def _mixed04(n=120, **kw):
+    return _mixed(R.PRESET_INW04_REFSET, n, **{"width": 64, "height": 48, "spp": 8, "max_bounces": 8, **kw})
+
+
+MIXED_CASES = ["inw01_mixed_moving", "inw01_mixed_moving_back", "inw01_mixed_spp37", "inw04_mixed_moving"]
+SHRUNK_CASES = ["inw01_mixed_shrunk06", "inw01_mixed_shrunk06_back", "inw04_mixed_shrunk09"]
+
 CASES = {
     # name: callable -> Scene (IOW-01 handled separately)
     "iow03_ref3": lambda: _scene(R.PRESET_IOW03_REF3, spp=4),
@@ -115,6 +181,18 @@ CASES = {
     "inw01_random_focus1": lambda: _scene_cam(R.PRESET_INW01_RANDOM, 1234, 3000, {"focus_dist": 1.05},
                                               width=48, height=27, spp=8),
     "inw01_dense_glass": lambda: _dense_glass(160, width=48, height=48, spp=6, max_bounces=10),
+    # moving rotated unequal-scale ellipsoids and cuboids (the 7-float4 records with time bins, bin
+    # boxes from rotation, scale and delta), from both sides (the reference's two child orders);
+    # ragged 8x8 units with spp no multiple of the wave or the bin count; INW-04 with moving lights
+    "inw01_mixed_moving": lambda: _mixed01(),
+    "inw01_mixed_moving_back": lambda: _mixed01(back=True),
+    "inw01_mixed_spp37": lambda: _mixed01(60, width=33, height=21, spp=37),
+    "inw04_mixed_moving": lambda: _mixed04(),
+    # the same scenes with caller boxes the objects stick out of (shrunk to 0.6 / 0.9 of their size):
+    # the reference's winner depends on the boxes and on the child order
+    "inw01_mixed_shrunk06": lambda: _mixed01(shrink=0.6),
+    "inw01_mixed_shrunk06_back": lambda: _mixed01(back=True, shrink=0.6),
+    "inw04_mixed_shrunk09": lambda: _mixed04(shrink=0.9),
 }
 
 GOLDEN_CASES = ["iow01_c1", "iow03_ref3", "iow03_ref3_normals", "iow03_final", "inw01_grid",

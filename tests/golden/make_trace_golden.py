@@ -1,4 +1,5 @@
-"""Regenerate tests/golden/trace_*.npz: scenes, 2048 ray queries each, and the reference answers
+"""Regenerate tests/golden/trace_*.npz: scenes, 2048 ray queries each (4096 for the shrunk-box
+scenes), and the reference answers
 of tests/trace_ref.c (the CPU oracle's closest-hit walk per query) for both child orders.
 
 Each fixture is self-contained: geom (N, 28), aabbs (N, 6), nodes (2N - 1, 8), layout, rays
@@ -66,6 +67,25 @@ def scene_mixed700():
     return _pack(objs), 1
 
 
+def scene_shrunk(factor):
+    """200 mixed moving objects whose caller-supplied boxes are the packers' shrunk about their centres
+    to `factor` of their size, with the LBVH over the shrunk boxes: the objects stick out of their leaf
+    boxes, and the reference (which culls with whatever boxes it is given, and tests a leaf box against
+    its running limit) answers differently for the two child orders."""
+    rng = np.random.default_rng(61)
+    objs = []
+    for i in range(200):
+        p = rng.uniform(-3.0, 3.0, 3)
+        last = p - rng.uniform(-0.4, 0.4, 3) if i % 3 != 2 else p
+        objs.append((R.RT_INW_ELLIPSOID if i % 2 == 0 else R.RT_INW_CUBOID, p, last, rng.uniform(-90, 90, 3),
+                     rng.uniform(0.4, 1.4, 3)))
+    geom, aabbs, _ = _pack(objs)
+    a = aabbs.astype(np.float64)
+    mid, half = (a[:, 0:3] + a[:, 3:6]) / 2, (a[:, 3:6] - a[:, 0:3]) / 2 * factor
+    aabbs = np.ascontiguousarray(np.concatenate([mid - half, mid + half], axis=1), np.float32)
+    return (geom, aabbs, R.lbvh_build(aabbs)), 1
+
+
 def scene_small(n, seed):
     return _pack(_spheres(np.random.default_rng(seed), n, half=(2.0, 1.0, 2.0), r=(0.5, 1.2), move=0.2)), 1
 
@@ -97,8 +117,12 @@ SCENES = {
     "dups300": scene_dups300,
     "pile120": scene_pile120,
     "refset4": scene_refset4,
+    "shrunk06": lambda: scene_shrunk(0.6),
+    "shrunk09": lambda: scene_shrunk(0.9),
 }
 SEEDS = {name: 100 + i for i, name in enumerate(SCENES)}
+SEEDS["shrunk09"] = SEEDS["shrunk06"]  # the same queries against both sets of boxes (aimed at the objects)
+QUERIES = {"shrunk06": 4096, "shrunk09": 4096}  # Q for the others
 
 
 def _unit(v):
@@ -153,7 +177,7 @@ def main():
             if only and name not in only:
                 continue
             (geom, aabbs, nodes), layout = SCENES[name]()
-            rays = make_rays(geom, aabbs, SEEDS[name])
+            rays = make_rays(geom, aabbs, SEEDS[name], QUERIES.get(name, Q))
             out = {"geom": geom, "aabbs": aabbs, "nodes": nodes, "layout": np.int32(layout),
                    "rays": rays.view(np.float32).reshape(-1, 8)}
             for inv in (0, 1):

@@ -44,6 +44,13 @@ def dev_scene(f: _Fx):
     return s
 
 
+def _wide_nodes(s) -> int:
+    """rt_debug_wide_info: the nodes of the scene's wide tree (0: its queries take the reference walk)."""
+    info = (C.c_uint32 * 8)()
+    assert R.load().rt_debug_wide_info(s, info, None) == 0
+    return int(info[0])
+
+
 def trace_async(s, rays, flags, n_rays=None, cap=None):
     """rt_trace_rays_async on the current torch stream; the hit buffer (cap records) starts as
     SENTINEL bytes.  Returns (rc, hits (cap,), counters (6,))."""
@@ -105,7 +112,7 @@ def test_batch_sizes_and_untouched_tail(gpu):
 
 @pytest.mark.parametrize("option", ["inw_wide_walk", "inw_time_bins", "inw_sphere_records", "inw_compact_nodes",
                                     "inw_stackless", "inw_fused_cull"])
-@pytest.mark.parametrize("name", ["spheres1500", "mixed700", "dups300", "pile120"])
+@pytest.mark.parametrize("name", ["spheres1500", "mixed700", "dups300", "pile120", "shrunk06", "shrunk09"])
 def test_options_do_not_change_results(gpu, name, option):
     f = fx(name)
     with R.options(**{option: 0}):
@@ -131,6 +138,33 @@ def test_updated_scene_traces_as_the_new_frame(gpu, device_build):
             assert rc == R.RT_OK
             assert_same(hits, b.hits[invert], f"updated scene, invert {invert}")
             assert ctr[0] == len(b.rays) and ctr[4] == b.drops[invert]
+    finally:
+        lib.rt_dev_scene_free(s)
+
+
+@pytest.mark.parametrize("device_build", [False, True])
+def test_updated_scene_with_boxes_objects_stick_out_of(gpu, device_build):
+    """mixed700 (the packers' boxes) updated to shrunk06, whose objects stick out of the caller's boxes
+    (tests/test_trace_ref.py): with the caller's nodes, and with nodes = NULL and the shrunk boxes.  The
+    answers follow the boxes given, for both child orders, and the scene no longer takes the wide
+    walk (DESIGN.md §2 "Objects inside their leaf boxes")."""
+    a, b = fx("mixed700"), fx("shrunk06")
+    lib = R.load()
+    s = dev_scene(a)
+    try:
+        rc, hits, _ = trace_async(s, a.rays, 0)
+        assert rc == R.RT_OK
+        assert_same(hits, a.hits[0], "mixed700 before the update")
+        assert _wide_nodes(s) > 0
+        rc = lib.rt_dev_scene_inw_update(s, R.fptr(b.geom), b.n, None if device_build else R.fptr(b.nodes),
+                                         R.fptr(b.aabbs) if device_build else None, None, 0, None)
+        assert rc == R.RT_OK
+        for invert in (0, 1):
+            rc, hits, ctr = trace_async(s, b.rays, invert * R.RT_TRACE_INVERT)
+            assert rc == R.RT_OK
+            assert_same(hits, b.hits[invert], f"updated to shrunk06, invert {invert}")
+            assert ctr[0] == len(b.rays) and ctr[4] == b.drops[invert]
+        assert _wide_nodes(s) == 0
     finally:
         lib.rt_dev_scene_free(s)
 

@@ -46,6 +46,18 @@ def _check_dump(d, c, build):
     assert W.reported(res) == {}, {k: v[:3] for k, v in res.items() if v}
 
 
+def _check_bin_tree(d, c, bins, b, **kw):
+    """Bin tree b of a dump: its leaf slots hold rt_debug_bin_boxes' boxes (the library's own), and the
+    objects themselves: the boxes of walk_struct_ref.inw_samples' surface points at the bin's two end
+    ratios (float64, exact comparison; the object moves on a straight line between them)."""
+    root = 1 + d["n_wtree0"] + b * d["wbin_stride"]
+    v = W.check_wide_tree(d["wnodes"], root, c.n, K.bin_boxes(c.geom, c.n, bins, b), **kw)
+    assert v == [], (b, v[:3])
+    own = W.inw_sample_boxes(c.geom, (b / bins, (b + 1) / bins), W.unit_dirs(100))
+    v = W.check_wide_tree(d["wnodes"], root, c.n, own)
+    assert v == [], (b, v[:3])
+
+
 def _check_ri_equals_host(d, n):
     """The device RI grid against ri_grid_build over the same (dumped) leaf boxes: equal frame, equal
     offsets, equal id sets per cell (the device fill is atomic: no order within a cell)."""
@@ -102,11 +114,11 @@ def test_device_build_past_the_level_cap_falls_back_to_the_host(gpu):
     _check_dump(d, c, 2)
     assert d["wbins"] == 2 and len(d["wnodes"]) == d["n_wtree0"] + 2 * d["wbin_stride"]
     for b in range(2):
-        v = W.check_wide_tree(d["wnodes"], 1 + d["n_wtree0"] + b * d["wbin_stride"], c.n, K.bin_boxes(c.geom, c.n, 2, b))
-        assert v == [], (b, v[:3])
+        _check_bin_tree(d, c, 2, b)
 
 
-@pytest.mark.parametrize("name,bins", [("random600", 2), ("random600", 4), ("random600_at990", 4), ("cornell", 2)])
+@pytest.mark.parametrize("name,bins", [("random600", 2), ("random600", 4), ("random600_at990", 4), ("cornell", 2),
+                                       ("mixed250", 2), ("mixed250", 4), ("mixed120_l4", 2), ("mixed120_l4", 4)])
 def test_fresh_scene_derived_nodes(gpu, name, bins):
     """A fresh host-built scene dumped from the device: the wide nodes are the host builders' bytes, and
     the compact and quantised nodes (always made by the two device kernels) pass their checks over every
@@ -124,9 +136,7 @@ def test_fresh_scene_derived_nodes(gpu, name, bins):
     assert d["wnodes"].tobytes() == wn.tobytes() and d["lbvh"].tobytes() == c.nodes.tobytes()
     _check_dump(d, c, 0)
     for b in range(nb if nb > 1 else 0):
-        v = W.check_wide_tree(d["wnodes"], 1 + n0 + b * stride, c.n, K.bin_boxes(c.geom, c.n, bins, b),
-                              wbound=d["wbound"])
-        assert v == [], (b, v[:3])
+        _check_bin_tree(d, c, bins, b, wbound=d["wbound"])
     h = R.inw_host_dump(c.nodes, c.n)
     assert h["rank"].tobytes() == d["rank"].tobytes() and h["dfs_high"] == d["dfs_high"]
     if d["ri_grid"]:

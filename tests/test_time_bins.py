@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 import rt_amd as R
+import walk_struct_cases as K
+import walk_struct_ref as W
 
 
 def _time_bins(sc, bins):
@@ -109,3 +111,53 @@ def test_sphere_records():
     cb = R.make_scene(R.PRESET_INW04_CORNELL, 7, 0, width=8, height=8, spp=1)
     g4 = np.ascontiguousarray(cb.geom, np.float32)
     assert lib.rt_debug_sphere_records(R.fptr(g4), cb.n, 4, R.fptr(np.zeros((cb.n, 12), np.float32))) == 0
+
+
+@pytest.mark.parametrize("bins", [2, 4, 7, 16])
+@pytest.mark.parametrize("name", ["mixed250", "mixed120_l4"])
+def test_bin_boxes_hold_rotated_moving_objects(name, bins):
+    """inw_bin_boxes derives its boxes from rotation, scale and delta.  Against the geometry itself
+    (walk_struct_ref.inw_samples: float64 surface points placed as the oracle's intersect_ray places the
+    object, no code shared with the library): every sample of every moving, rotated, unequal-scale
+    ellipsoid and cuboid at the bin's two end ratios and its middle lies inside the bin's box, in exact
+    comparison.  (The boxes are inflated by at least 1e-3, so the worst margin is printed too.)"""
+    c = K.case(name)
+    dirs = W.unit_dirs(400)
+    worst = np.inf
+    for b in range(bins):
+        v, m = W.check_bin_boxes(c.geom, bins, b, K.bin_boxes(c.geom, c.n, bins, b), dirs)
+        assert v == [], v[:3]
+        worst = min(worst, m)
+    print(name, bins, "worst margin", worst)
+    assert worst > 0.0
+
+
+def test_bin_box_checker_reports_a_box_shrunk_by_one_percent_on_one_side():
+    """The checker can fail: one face of one object's box moved inward by 1% of the box's size is
+    reported, for that object alone.  The faces are those the boxes fit tightly: of the ellipsoids,
+    along the axis where the larger of the two norms inw_bin_boxes takes is the object's true extent
+    (a cuboid's box, sized by the same norm, is at least 15% larger than its corners need), a low and a
+    high face of a moving and of a static one."""
+    c = K.case("mixed250")
+    dirs = W.unit_dirs(400)
+    bins, b = 4, 2
+    clean = K.bin_boxes(c.geom, c.n, bins, b)
+    assert W.check_bin_boxes(c.geom, bins, b, clean, dirs)[0] == []
+    ratios = [(b + h) / bins for h in (0.0, 0.5, 1.0)]
+    slack = np.abs(W.inw_sample_boxes(c.geom, ratios, dirs) - clean) / np.tile(clean[:, 3:6] - clean[:, 0:3], 2)
+    ell = (c.geom[:, 18] + 0.1).astype(int) == W.INW_ELLIPSOID
+    moving = (c.geom[:, 15:18] != 0).any(axis=1)
+    done = 0
+    for sel in (ell & moving, ell & ~moving):
+        for cols in ((0, 1, 2), (3, 4, 5)):
+            sub = np.where(sel[:, None], slack[:, cols], np.inf)
+            g, k = np.unravel_index(np.argmin(sub), sub.shape)
+            col = cols[k]
+            assert slack[g, col] < 0.005  # a tight face: within half a percent of the box's size
+            boxes = clean.copy()
+            size = clean[g, 3 + col % 3] - clean[g, col % 3]
+            boxes[g, col] += np.float32(0.01) * size * (1 if col < 3 else -1)
+            v, m = W.check_bin_boxes(c.geom, bins, b, boxes, dirs)
+            assert [kind for kind, _ in v] == ["bin_box"] and f"object {g}:" in v[0][1] and m < 0, (g, col, v)
+            done += 1
+    assert done == 4

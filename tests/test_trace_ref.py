@@ -1,12 +1,16 @@
 """The ray-query fixtures (tests/golden/trace_*.npz) against their reference, on the CPU:
 tests/trace_ref.c -- the oracle's own closest-hit walk per query -- is rebuilt and recomputes
 every fixture bit for bit, and the fixtures exercise what the GPU tests rely on them for: hits
-and misses in every scene, exact ties decided by the child order (dups300), and pushes the full
-40-float stack drops (pile120)."""
+and misses in every scene, exact ties decided by the child order (dups300), pushes the full
+40-float stack drops (pile120), and caller boxes that the objects stick out of, where the winner depends
+on the child order and lies far in front of its own leaf box (shrunk06, shrunk09)."""
 import numpy as np
 import pytest
 
 import trace_ref as T
+
+
+SHRUNK = ("shrunk06", "shrunk09")  # objects stick out of their boxes (test_shrunk_boxes_are_adversarial)
 
 
 @pytest.fixture(scope="module")
@@ -19,7 +23,7 @@ def test_fixture_recomputes_bit_for_bit(ref_lib, name):
     fx = T.load_fixture(name)
     n = fx["geom"].shape[0]
     assert fx["geom"].shape == (n, 28) and fx["nodes"].shape == (2 * n - 1, 8) and fx["aabbs"].shape == (n, 6)
-    assert fx["rays"].shape == (2048,) and fx["layout"] in (1, 4)
+    assert fx["rays"].shape == (4096 if name in SHRUNK else 2048,) and fx["layout"] in (1, 4)
     for inv in (0, 1):
         hits, ctr = T.run(ref_lib, fx["geom"], fx["nodes"], fx["layout"], fx["rays"], inv)
         assert T.same_hits(hits, fx[f"hits{inv}"]), (name, inv)
@@ -42,8 +46,8 @@ def test_fixture_hits_are_well_formed(name):
         assert not h["n"][~hit].any() and not h["extra"][~hit].any() and not h["pad"].any()
         # a hit's extra is its object's record float 19
         assert np.array_equal(h["extra"][hit].view(np.uint32), fx["geom"][h["id"][hit], 19].view(np.uint32))
-    # the child order changes no hit mask unless a push dropped
-    if not fx["ctr0"][2] and not fx["ctr1"][2]:
+    # the child order changes no hit mask unless a push dropped (objects inside their boxes)
+    if not fx["ctr0"][2] and not fx["ctr1"][2] and name not in SHRUNK:
         assert np.array_equal(fx["hits0"]["id"] >= 0, fx["hits1"]["id"] >= 0)
         assert np.array_equal(fx["hits0"]["t"].view(np.uint32), fx["hits1"]["t"].view(np.uint32))
 
@@ -79,3 +83,34 @@ def test_update_pair_shares_objects():
     assert a["geom"].shape == b["geom"].shape
     assert np.array_equal(a["geom"][:, 12:15], b["geom"][:, 12:15])  # scales
     assert np.all(np.any(a["geom"][:, 0:3] != b["geom"][:, 0:3], axis=1))
+
+
+def _winner_box_entry(fx, hits):
+    """(entry t of each winner's own leaf box along its ray, the winner's t), float64, for the hits."""
+    rays, hit = fx["rays"], hits["id"] >= 0
+    box = fx["aabbs"][hits["id"][hit]].astype(np.float64)
+    o, d = rays["o"][hit].astype(np.float64), rays["d"][hit].astype(np.float64)
+    with np.errstate(all="ignore"):
+        near = np.minimum((box[:, 0:3] - o) / d, (box[:, 3:6] - o) / d)
+    return np.where(d != 0, near, -np.inf).max(axis=1), hits["t"][hit].astype(np.float64)
+
+
+def test_shrunk_boxes_are_adversarial():
+    """What the shrunk-box fixtures are for.  The reference tests a leaf box against its running limit,
+    so with boxes the objects stick out of its answer depends on the child order; and a winner can lie
+    far in front of its own leaf box: beyond the wide walk's culling limit t * 1.0001 + 1e-3, which the
+    leaf-entry guard's argument assumes never happens.  With the packers' own boxes
+    (mixed700) neither occurs."""
+    fx = T.load_fixture("shrunk06")
+    assert fx["geom"].shape[0] == 200 and int((fx["geom"][:, 15:18] != 0).any(axis=1).sum()) > 100
+    assert int((fx["hits0"]["id"] != fx["hits1"]["id"]).sum()) >= 100
+    for name, least in (("shrunk06", 500), ("shrunk09", 100)):
+        fx = T.load_fixture(name)
+        for k in ("hits0", "hits1"):
+            te, t = _winner_box_entry(fx, fx[k])
+            assert int((te > t * 1.0001 + 1e-3).sum()) >= least, (name, k)
+    fx = T.load_fixture("mixed700")
+    assert np.array_equal(fx["hits0"]["id"], fx["hits1"]["id"])
+    for k in ("hits0", "hits1"):
+        te, t = _winner_box_entry(fx, fx[k])
+        assert int((te > t * 1.0001 + 1e-3).sum()) == 0

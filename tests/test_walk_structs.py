@@ -209,7 +209,7 @@ def test_host_built_structures_are_conservative(name):
 
 
 @pytest.mark.parametrize("bins", [2, 4])
-@pytest.mark.parametrize("name", ["random600", "random257", "random5", "random600_at990"])
+@pytest.mark.parametrize("name", ["random600", "random257", "random5", "random600_at990", "mixed250", "mixed120_l4"])
 def test_host_built_bin_trees_are_conservative(name, bins):
     """inw_wide_add_bins: the swept tree unchanged in front, then one tree per bin whose leaf slots
     contain rt_debug_bin_boxes' box of the object (test_time_bins.py checks those boxes against the
@@ -223,6 +223,10 @@ def test_host_built_bin_trees_are_conservative(name, bins):
     assert W.check_wide_tree(wn, 1, c.n, W.swept_boxes(d["leafbox"]), n_nodes=n0, depth=d["depth"]) == []
     for b in range(bins):
         v = W.check_wide_tree(wn, 1 + n0 + b * stride, c.n, K.bin_boxes(c.geom, c.n, bins, b))
+        assert v == [], (b, v[:3])
+        # ... and the objects themselves at the bin's two end ratios (walk_struct_ref.inw_samples)
+        own = W.inw_sample_boxes(c.geom, (b / bins, (b + 1) / bins), W.unit_dirs(100))
+        v = W.check_wide_tree(wn, 1 + n0 + b * stride, c.n, own)
         assert v == [], (b, v[:3])
         # padding nodes behind the tree are empty
         assert (W.links_of(wn[n0 + b * stride:n0 + (b + 1) * stride]) != W.EMPTY).any(axis=1).sum() <= stride

@@ -12,7 +12,8 @@ ROOT = os.path.dirname(HERE)
 GOLDEN = os.path.join(HERE, "golden")
 
 # the trace_*.npz fixtures, in the order the generator writes them
-SCENES = ["spheres1500", "spheres1500_b", "mixed700", "one", "three", "dups300", "pile120", "refset4"]
+SCENES = ["spheres1500", "spheres1500_b", "mixed700", "one", "three", "dups300", "pile120", "refset4",
+          "shrunk06", "shrunk09"]
 
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("ratio", np.float32)])
 HIT_DTYPE = np.dtype([("t", np.float32), ("id", np.int32), ("n", np.float32, 3), ("extra", np.float32),

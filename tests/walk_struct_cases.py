@@ -97,6 +97,12 @@ def _make():
     # coordinates approach +990 in x and -990 in y (the fused cull's condition is 1000)
     off = (990.0 - float(base.aabbs[:, 3].max()), -990.0 - float(base.aabbs[:, 1].min()), 0.0)
     out.append(_translated("random600_at990", base, off))
+    # moving rotated unequal-scale ellipsoids and cuboids (tests/cases.py _mixed): the bin boxes come from
+    # rotation, scale and delta
+    import cases as frames
+    for name, sc in (("mixed250", frames.CASES["inw01_mixed_moving"]()), ("mixed120_l4", frames.CASES["inw04_mixed_moving"]())):
+        out.append(Case(name, np.ascontiguousarray(sc.geom, np.float32), np.ascontiguousarray(sc.aabbs, np.float32),
+                        layout=sc.layout, lights=sc.lights if sc.n_lights else None))
     out.append(_preset("refset5", R.PRESET_INW04_REFSET, 0, 0))  # (not in NAMES: the INW-04 scene updates start from)
     return out
 
@@ -112,7 +118,7 @@ def cases():
 
 
 NAMES = ["random600", "random2000", "grid9", "cornell", "random2", "random3", "random5", "random257", "random1025",
-         "dups300", "coplanar400", "spanning501", "chain200", "random600_at990"]
+         "dups300", "coplanar400", "spanning501", "chain200", "random600_at990", "mixed250", "mixed120_l4"]
 
 
 def case(name):

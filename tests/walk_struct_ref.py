@@ -381,6 +381,60 @@ def iow_samples(typ, rec, dirs):
     return pos + local @ Minv.T
 
 
+INW_ELLIPSOID, INW_CUBOID = 1, 2
+
+
+def inw_samples(record28, ratio, dirs):
+    """World-space surface samples (float64) of one INW object (its 28-float GeometryBuff record) at one
+    time ratio, as the oracle's intersect_ray places it: centre p - delta (1 - ratio) (p floats 0..2,
+    delta 15..17), world point = centre + R local with R's columns floats 3..5, 6..8 and 9..11 (the ray
+    goes to object space by R transposed).  Ellipsoid (float 18 = 1): local = scale * unit direction,
+    for `dirs`, the +-axes and the six directions whose image is extreme along a world axis; cuboid
+    (2): its eight corners +-scale / 2."""
+    f = np.asarray(record28, np.float64)
+    centre = f[0:3] - f[15:18] * (1.0 - float(ratio))
+    Rm = np.stack([f[3:6], f[6:9], f[9:12]], axis=1)
+    scale = np.abs(f[12:15])
+    if int(f[18] + 0.1) == INW_ELLIPSOID:
+        # world_k = sum_c R[k, c] scale_c u_c over unit u: extreme at u along (R[k, c] scale_c)_c
+        ext = [s * (Rm[k] * scale) / np.linalg.norm(Rm[k] * scale) for k in range(3) for s in (-1.0, 1.0)]
+        u = np.concatenate([dirs, np.eye(3), -np.eye(3), np.array(ext)])
+        local = u * scale
+    else:
+        local = np.array([[sx, sy, sz] for sx in (-.5, .5) for sy in (-.5, .5) for sz in (-.5, .5)]) * scale
+    return centre + local @ Rm.T
+
+
+def unit_dirs(n, seed=5):
+    d = np.random.default_rng(seed).normal(size=(n, 3))
+    return d / np.linalg.norm(d, axis=1)[:, None]
+
+
+def inw_sample_boxes(geom, ratios, dirs):
+    """(n, 6) float64: the box of every object's samples over `ratios` (lo xyz, hi xyz)."""
+    out = np.zeros((len(geom), 6))
+    for g, rec in enumerate(geom):
+        s = np.concatenate([inw_samples(rec, r, dirs) for r in ratios])
+        out[g, 0:3], out[g, 3:6] = s.min(axis=0), s.max(axis=0)
+    return out
+
+
+def check_bin_boxes(geom, bins, b, boxes, dirs):
+    """boxes (n, 6) float32, the culling boxes of time bin b of `bins`: every surface sample of every
+    object at the ratios b / bins, (b + 1/2) / bins and (b + 1) / bins lies inside its box, in exact
+    comparison ("bin_box").  Also returns the smallest margin (box face to the nearest sample beyond
+    which it lies; negative: a violation)."""
+    v, worst = [], np.inf
+    bx = np.asarray(boxes, np.float64)
+    for g, rec in enumerate(geom):
+        s = np.concatenate([inw_samples(rec, (b + h) / bins, dirs) for h in (0.0, 0.5, 1.0)])
+        m = min(float((s - bx[g, 0:3]).min()), float((bx[g, 3:6] - s).min()))
+        worst = min(worst, m)
+        if not ((s >= bx[g, 0:3]).all() and (s <= bx[g, 3:6]).all()):
+            v.append(("bin_box", f"bin {b} of {bins}, object {g}: a surface sample lies outside its box by {-m}"))
+    return v, worst
+
+
 def check_iow_cull(types, records, wide, obox, n_dirs=300, seed=3):
     """The IOW-03 culling BVH (wide (N, 32): six float4 of child planes, the links as int bits) and the
     object boxes obox (n, 6): the tree checks of check_wide_tree against obox, and obox[j] contains
