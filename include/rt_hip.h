@@ -681,7 +681,9 @@ int rt_pixels_iow03(const float *types, const float *records /* N*24 */, uint32_
  * p or d_state, bad params as the renders judge them, p->spp != the scene's, s0 >= p->spp or a scene
  * a failed update left broken; then RT_E_UNSUPPORTED for p->show_normal != 0.  ns == 0 returns RT_OK
  * and launches nothing; s0 + ns may overrun S (the pass is clipped).  Not covered: packed tile lists,
- * device groups and the MULTIFOCUS camera (no device scene has one: only rt_render_inw_mf's own). */
+ * device groups and the MULTIFOCUS camera (no device scene has one: only rt_render_inw_mf's own).
+ * Packed pixel lists, with a sample count per pixel, are served by rt_render_pass_pixels_async below;
+ * "Captured graphs" there states a rule that was seen to hold for captured passes as well. */
 typedef struct rt_pass_state { float acc[3]; float depth; float ri[4]; } rt_pass_state;   /* 32 B */
 /* Device pointers (16-byte aligned). */
 int rt_render_pass_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p,
@@ -702,6 +704,94 @@ int rt_render_passes_inw(const float *geom, uint32_t n, int layout, const float 
 int rt_render_passes_iow03(const float *types, const float *records /* N*24 */, uint32_t n, const rt_camera *cam,
                            const rt_params *p, const uint32_t *cuts, int n_cuts, float *rgba /* n_cuts*W*H*4 */,
                            rt_pass_state *state_out /* W*H, may be NULL */, int device, rt_stats *st);
+
+/* ---- adaptive sample passes ------------------------------------------------------------------
+ * Refinement that stops where the image has settled: a pass over a packed pixel list in which every
+ * pixel continues from its own sample count, a device-side error estimate, and the ordered compaction
+ * of the pixels that still need samples.  The sequential folds that make the passes above exact make
+ * this exact too: a pixel that stopped after n samples holds, bit for bit, the state and image
+ * rt_render_pass_async gives every pixel after n samples.
+ *
+ * rt_pass_aux is what a pixel keeps beside its rt_pass_state: count, the samples folded so far, and
+ * even, the same fold as acc restricted to the even sample indices (0, 2, 4, ...) in sample order
+ * (INW: sample 0's sqrt(colour) assigned, the later even samples added; IOW-03: a sum of rgb from
+ * 0.0f).  A frame starts from a zeroed aux buffer; the state needs no memset.
+ *
+ * rt_render_pass_pixels_async handles every listed pixel inside the image: with c =
+ * d_aux[y * W + x].count it renders samples [c, min(c + ns, S)) of that pixel, S as for
+ * rt_render_pass_async, continues d_state (not read when c == 0) and aux.even, sets aux.count to the
+ * new count c', writes acc * RN(1 / c') with alpha 1 to d_rgba and the state's depth to d_depth, and
+ * adds to the counters as the passes do.  A listed pixel with c >= S renders nothing and has its image
+ * rewritten from its state.  Unlisted pixels keep every byte of state, aux and image; an entry outside
+ * [0, W) x [0, H) is skipped, so a host can launch with the list's full capacity without reading the
+ * count back (rt_pass_select_async pads the list with {-1, -1}).  The list holds no pixel twice: the
+ * caller's duty, unchecked.  p->tile_* is ignored.  The scene's options apply as for the passes.
+ * Never synchronises; on an INW scene the first call of a list size and sample count grows the scene's
+ * pass workspace (64 B per entry and sample of a chunk), later ones allocate nothing, so they are
+ * graph-capturable, with the condition stated under "Captured graphs" below.  Calls on one scene must
+ * not overlap each other, its passes, renders or queries.
+ * Returns RT_E_ARG, before a device is touched and with the buffers untouched, for a null scene, cam,
+ * p, d_state or d_aux, null d_pixels with n_pixels > 0, n_pixels > 2^31, bad params as the renders
+ * judge them, p->spp != the scene's or a scene a failed update left broken; then RT_E_UNSUPPORTED for
+ * p->show_normal != 0.  n_pixels == 0 or ns == 0 returns RT_OK and launches nothing.
+ *
+ * rt_pass_select_async works on the rectangle p->tile_* (the whole frame when 0).  With n = count,
+ * h = (n + 1) / 2, a = acc * RN(1 / n) and e = even * RN(1 / h), all in binary32 in this order,
+ *   err = (|a.x - e.x| + |a.y - e.y|) + |a.z - e.z|,   err = +inf for n < 2,
+ * and a pixel is active iff n < S && (n < min_samples || !(err <= tol)): a NaN estimate keeps the pixel
+ * sampling, and tol < 0 keeps every pixel active until S.  d_list[0 .. n_active) receives the active
+ * pixels in the order of the passes' units (8x8 blocks of the rectangle row-major, pixels row-major
+ * inside a block, units past the rectangle's edge left out), the remaining entries {-1, -1} up to the
+ * count of the rectangle's pixels that lie inside the image (entries past that count keep their bytes:
+ * a rectangle that leaves the image is clipped); *d_n_active the active count; d_err[y * W + x], when given, the
+ * estimate of the rectangle's pixels (pixels outside it keep their bytes).  Three launches, no
+ * synchronisation, no allocation beyond a scratch the scene owns (8 B per 256 units; the first call of
+ * a rectangle size grows it); after that call it is graph-capturable, with the condition below.
+ * RT_E_ARG for a null scene, p, d_state, d_aux, d_list or d_n_active, bad params, p->spp != the scene's
+ * or a broken scene.
+ *
+ * Captured graphs: a known condition, cause unknown.  Before a graph of these calls is captured, run its
+ * calls once eagerly ON THE STREAM THE GRAPH WILL BE REPLAYED ON.  Where the eager run had been on
+ * another stream only, the first replay gave the eager bytes and every later replay gave wrong images:
+ * the persistent kernels of the later rounds (k_inw_paths, k_iow_adapt, and k_iow_pass alike) found
+ * their work-queue word used up, as if the 4-byte hipMemsetAsync node that zeroes it before each of
+ * them had lost its order against them (node pair: queue memset -> persistent kernel).  This was seen
+ * on graphs of rt_render_pass_pixels_async + rt_pass_select_async, of rt_render_pass_async +
+ * rt_pass_select_async and, in the same probe, of three rt_render_pass_async calls alone, so it is not
+ * particular to these two calls; with the eager run on the replay's stream every replay observed was
+ * right (DESIGN.md 5.14 has the probes).  Nothing in the library's host or device code reads the
+ * stream apart from launching on it. */
+typedef struct rt_pass_aux { float even[3]; uint32_t count; } rt_pass_aux;   /* 16 B per pixel */
+/* Device pointers (16-byte aligned; d_pixels and d_list 8-byte). */
+int rt_render_pass_pixels_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p,
+                                const rt_pixel *d_pixels, uint32_t n_pixels, uint32_t ns,
+                                rt_pass_state *d_state /* W*H */, rt_pass_aux *d_aux /* W*H */,
+                                float *d_rgba /* may be NULL */, float *d_depth /* may be NULL */,
+                                uint64_t *d_counters /* may be NULL */, void *stream);
+int rt_pass_select_async(rt_dev_scene *s, const rt_params *p,
+                         const rt_pass_state *d_state, const rt_pass_aux *d_aux,
+                         float tol, uint32_t min_samples,
+                         rt_pixel *d_list /* one entry per pixel of the rectangle */,
+                         uint32_t *d_n_active, float *d_err /* W*H, may be NULL */, void *stream);
+/* Blocking: host buffers; build a device scene for the call like rt_render_passes_inw / _iow03 and run
+ * the loop: zero the aux buffer and list every pixel of the rectangle; one listed pass with ns = batch;
+ * select, and read n_active back; again while n_active > 0 and rounds remain (max_rounds == 0: no
+ * limit; the loop ends by itself once every pixel has S samples).  rgba (and depth) hold the image of
+ * the last pass each pixel was in; pixels outside the rectangle keep the bytes the buffers came with.
+ * May be NULL: count (W*H, the samples per pixel), err (W*H, the last select's estimate), state_out,
+ * aux_out, rounds_out (the rounds run), st (the counters and the rounds' summed device time).
+ * RT_E_ARG also for null rgba or batch == 0. */
+int rt_render_adaptive_inw(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                           uint32_t n_lights, const rt_texture *tex, int n_tex, const rt_camera *cam,
+                           const rt_params *p, uint32_t batch, float tol, uint32_t min_samples,
+                           uint32_t max_rounds, float *rgba /* W*H*4 */, float *depth /* W*H or NULL */,
+                           uint32_t *count, float *err, rt_pass_state *state_out, rt_pass_aux *aux_out,
+                           uint32_t *rounds_out, int device, rt_stats *st);
+int rt_render_adaptive_iow03(const float *types, const float *records /* N*24 */, uint32_t n, const rt_camera *cam,
+                             const rt_params *p, uint32_t batch, float tol, uint32_t min_samples,
+                             uint32_t max_rounds, float *rgba /* W*H*4 */, uint32_t *count, float *err,
+                             rt_pass_state *state_out, rt_pass_aux *aux_out, uint32_t *rounds_out, int device,
+                             rt_stats *st);
 
 /* ---- multi-GPU partition (BASELINE configs[3]) -----------------------------
  * One host thread drives several devices of this process: the frame's tiles are dealt

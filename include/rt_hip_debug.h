@@ -227,6 +227,15 @@ int rt_debug_pixels_kernel(int which, int info[4]);
  * returns the previous cap. */
 int rt_debug_pass_kernel(int which, int info[4]);
 int rt_debug_pass_max_blocks(int blocks);
+/* The adaptive-pass kernels (rt_render_pass_pixels_async, rt_pass_select_async) answer to
+ * rt_debug_pass_kernel as well: which = 8 is k_adapt_rays, 9 k_adapt_fold (both INW), 10 the IOW-03 kernel
+ * k_iow_adapt with the BVH staged in LDS, 11 the one that reads nodes from global memory, 12 k_select_count,
+ * 13 k_select_scan, 14 k_select_scatter.  (4..7 stay RT_E_ARG, as every value past 3 was before these
+ * kernels existed.)  rt_debug_pass_max_blocks also caps the grids of a listed pass.
+ * rt_debug_adaptive_chunk caps the samples of one chunk of an INW listed pass (0 = the default: as many as
+ * the workspace rule allows), so that a test can make a small pass run in several chunks; it returns the
+ * previous cap. */
+int rt_debug_adaptive_chunk(int samples);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,448 @@
+// rt_adaptive.hip -- adaptive sample passes on a device scene (rt_render_pass_pixels_async,
+// rt_pass_select_async): a pass over a packed pixel list in which every pixel continues from its own
+// sample count, and the ordered compaction of the pixels that still need samples.
+//
+// A listed pixel with count c renders samples [c, min(c + ns, S)) and folds them exactly as
+// rt_render_pass_async folds them (rt_passes.hip), so a pixel that stopped after n samples holds, bit for
+// bit, the state and image a uniform pass leaves after n samples.  Beside the state (rt_pass_state) a
+// pixel keeps an rt_pass_aux: its count and `even`, the same fold restricted to the even sample indices,
+// which the error estimate |acc / n - even / ceil(n / 2)| is formed from.
+//
+// INW: the composition of rt_passes.hip driven by the list -- k_adapt_rays writes the camera rays of
+// (entry, j < ns) as path queries, sample = count + j (the invalid sample past S or for an entry outside
+// the image), the unchanged path kernel answers them, k_adapt_fold folds an entry's answers in sample
+// order and advances its count, so the next chunk's rays start from the new count.
+// IOW-03: k_iow_adapt is k_iow_pass with the pixel, its first sample and its RI fields taken from the list
+// entry, the pixel's count and its state, and `even` folded beside the sum.  (k_iow_pass's loop is
+// repeated here, not shared through a header, so that kernel stays byte for byte what it was.)
+// Select: a stable partition of the rectangle's units (unit_pixel's order) in three plain launches --
+// per-block counts, an exclusive scan of the block partials in one block, the scatter.  No block waits on
+// another block.
+#include "rt_render_common.hpp"
+#include "rt_pass_common.hpp"
+#include "rt_inw_shade.hpp"
+#include "rt_iow_shade.hpp"
+
+namespace rtk {
+
+// Waves per SIMD of k_iow_adapt: k_iow_pass's (bound by LDS: 2 blocks per CU with the nodes staged, 3 without)
+template <bool LN> constexpr int kAdaptIowWaves = LN ? 2 : 3;
+
+// A list entry: inside the image or skipped ({-1, -1} is rt_pass_select_async's padding).
+__device__ __forceinline__ bool listed(const Frame &F, int2 p) {
+    return p.x >= 0 && p.y >= 0 && p.x < F.W && p.y < F.H;
+}
+
+// rt_pass_aux as the kernels read it: (even.xyz, count bits)
+__device__ __forceinline__ uint32_t aux_count(const float4 *aux, size_t out) { return __float_as_uint(aux[out].w); }
+
+// ------------------------------------------------------------------------------------------ INW
+// One lane per record: record k * ns + j is the camera ray of sample count + j of entry k's pixel, by the
+// render's own sample start; the sample is 0xffffffff, which the path kernel answers without a path, past
+// `stop` or for an entry outside the image.  n = n_pixels * ns <= 2^31.
+__global__ __launch_bounds__(kBlock)
+void k_adapt_rays(Frame Fin, InwScene S, const int2 *__restrict__ pixels, const float4 *__restrict__ aux,
+                  uint32_t stop, uint32_t ns, uint32_t n, float4 *__restrict__ rays) {
+    const uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+    if (i >= n) return;
+    Frame F{};
+    pass_frame(F, Fin);
+    const uint32_t k = i / ns, j = i - k * ns;
+    const int2 p = pixels[k];
+    float4 *r = rays + 2 * (size_t)i;
+    uint32_t s = 0xffffffffu;
+    if (listed(F, p)) {
+        const uint32_t c = aux_count(aux, (size_t)p.y * F.W + p.x);
+        if (c < stop && j < stop - c) s = c + j;
+    }
+    if (s != 0xffffffffu) {
+        PassRay K;
+        Ctr c;
+        inw_start_sample(S, F, K, p.x, p.y, (int)s, c);
+        r[0] = make_float4(K.o.x, K.o.y, K.o.z, __uint_as_float(s));
+        r[1] = make_float4(K.d.x, K.d.y, K.d.z, 0.0f);
+    } else {
+        r[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xffffffffu));
+        r[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
+// One lane per entry: End() over the entry's answers of samples [c, min(c + ns, stop)) in sample order,
+// from the pixel's state and aux (the state is not read when c == 0: the first sample is assigned) --
+// sqrt(colour) added to acc and, at even samples, to even; the depth of sample spp / 2 -- and the state,
+// the aux and the new count back.  last: the chunk is the pass's last, and the image acc * RN(1 / count)
+// and the depth are written (also for an entry that had nothing left to render).
+__global__ __launch_bounds__(kBlock)
+void k_adapt_fold(Frame Fin, const int2 *__restrict__ pixels, uint32_t n_pixels, uint32_t stop, uint32_t ns,
+                  uint32_t last, const float4 *__restrict__ out, float4 *__restrict__ state,
+                  float4 *__restrict__ aux) {
+    const uint32_t k = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+    if (k >= n_pixels) return;
+    Frame F{};
+    pass_frame(F, Fin);
+    const int2 p = pixels[k];
+    if (!listed(F, p)) return;
+    const size_t o = (size_t)p.y * F.W + p.x;
+    const uint32_t mid = (uint32_t)F.spp / 2u;
+    const float4 x = aux[o];
+    const uint32_t c = __float_as_uint(x.w);
+    f3 acc = f3{0, 0, 0}, ev = f3{x.x, x.y, x.z};
+    float dmid = 0.0f;
+    if (c != 0) {
+        const float4 a = state[2 * o];
+        acc = f3{a.x, a.y, a.z};
+        dmid = a.w;
+    }
+    const uint32_t m = c < stop ? (ns < stop - c ? ns : stop - c) : 0u;  // samples to fold
+    const float4 *a = out + 2 * (size_t)k * ns;
+    for (uint32_t j = 0; j < m; j++) {
+        const float4 r = a[2 * (size_t)j];
+        const f3 g = f3{__builtin_sqrtf(r.x), __builtin_sqrtf(r.y), __builtin_sqrtf(r.z)};
+        const uint32_t s = c + j;
+        acc = sel(s == 0, g, acc + g);
+        if ((s & 1u) == 0) ev = sel(s == 0, g, ev + g);
+        if (s == mid) dmid = r.w;
+    }
+    const uint32_t c1 = c + m;
+    if (m != 0) {
+        state[2 * o] = make_float4(acc.x, acc.y, acc.z, dmid);
+        aux[o] = make_float4(ev.x, ev.y, ev.z, __uint_as_float(c1));
+    }
+    if (!last) return;
+    if (F.out_rgba) {
+        const f3 v = acc * rcp((float)c1);
+        reinterpret_cast<float4 *>(F.out_rgba)[o] = make_float4(v.x, v.y, v.z, 1.0f);
+    }
+    if (F.out_depth) F.out_depth[o] = dmid;
+}
+
+// ------------------------------------------------------------------------------------------ IOW-03
+// k_iow_pass over the list: a persistent grid, a lane owns one entry's pixel at a time, a wave claims
+// 64 * rounds consecutive entries with one atomic and hands them to its free lanes by ballot and mbcnt.
+// The lane's samples are [count, min(count + ns, stop)); an entry with nothing left has its image
+// rewritten from its state.
+template <bool LN>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdaptIowWaves<LN>)))
+void k_iow_adapt(Frame Fin, IowScene S, const int2 *__restrict__ pixels, uint32_t stop, uint32_t ns,
+                 float4 *__restrict__ state, float4 *__restrict__ aux, unsigned *queue, uint32_t rounds,
+                 uint32_t n_units) {
+    Frame F{}, Fs{};
+    pass_frame(F, Fin);
+    pass_seg_frame(Fs, Fin);
+    using Cfg = IowCfg<false, 1, LN>;
+    using Stack = IowStack<false>;
+    __shared__ float lds[kIowStack * Stack::kSlot * kBlock];
+    __shared__ short lds_bvh[Cfg::BS * kBlock];
+    __shared__ float4 s_nodes[LN ? kIowLdsNodes * 7 : 1];
+    short *bstk = lds_bvh + threadIdx.x;  // bslot's layout
+    const float4 *nodes = iow_stage_nodes<LN>(S, s_nodes);
+    Ctr c;
+    Stack K{lds + threadIdx.x, nullptr, 0};
+    const uint32_t lane = threadIdx.x & 63u;
+    // out_Pixel's per-frame scalars (03...glsl:370-380); the per-pixel ones are kept per lane
+    const int grid = iow_ring_grid(F.spp);
+    const float aspect = iow_aspect(F.W, F.H);
+    const float dsx = iow_px_dsx(aspect, F.W, grid), dsy = iow_px_dsy(F.H, grid);
+    uint32_t next = 0, end = 0;  // the wave's claimed range not handed out yet (wave-uniform)
+    bool drained = false;        // the queue is empty (wave-uniform)
+    bool busy = false;           // the lane owns a pixel: samples [s, s1) are left
+    bool walking = false;        // ... and sample s's path is under way
+    uint32_t s = 0, s1 = 0, out = 0;  // out = y * W + x < 2^31
+    int skip = 0;
+    float sx = 0.0f, sy = 0.0f;
+    f3 fc = f3{0, 0, 0}, ev = f3{0, 0, 0}, col = f3{0, 0, 0};
+    for (;;) {
+        while (!drained) {  // hand entries to the free lanes
+            const unsigned long long free = __ballot(!busy);
+            if (free == 0) break;
+            if (next >= end) {
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(queue, 64u * rounds);
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                if (base >= n_units) { drained = true; break; }
+                next = base;
+                end = n_units - base < 64u * rounds ? n_units : base + 64u * rounds;  // n_units <= 2^31
+            }
+            const uint32_t avail = end - next, want = (uint32_t)__popcll(free);
+            const uint32_t rank = lanes_below(free);
+            if (!busy && rank < avail) {
+                const int2 p = pixels[next + rank];
+                if (listed(F, p)) {  // an entry outside the image: the lane stays free
+                    out = (uint32_t)p.y * (uint32_t)F.W + (uint32_t)p.x;
+                    const float4 x = aux[out];
+                    s = __float_as_uint(x.w);
+                    ev = f3{x.x, x.y, x.z};
+                    fc = f3{0, 0, 0};
+                    if (s == 0) {
+                        ev = f3{0, 0, 0};
+                        for (int e = 0; e < kIowStack; e++) K.at(e, 7) = 0.0f;  // stale RI slots start at 0
+                    } else {
+                        const float4 a = state[2 * (size_t)out], r = state[2 * (size_t)out + 1];
+                        fc = f3{a.x, a.y, a.z};
+                        K.at(0, 7) = r.x; K.at(1, 7) = r.y; K.at(2, 7) = r.z; K.at(3, 7) = r.w;
+                    }
+                    if (s < stop) {
+                        s1 = ns < stop - s ? s + ns : stop;
+                        sx = iow_px_sx(aspect, p.x, F.W);
+                        sy = iow_px_sy(p.y, F.H);
+                        busy = true;
+                    } else {  // nothing left to render: the image from the state as it is
+                        if (F.out_rgba) {
+                            const f3 v = fc * rcp((float)s);
+                            reinterpret_cast<float4 *>(F.out_rgba)[out] = make_float4(v.x, v.y, v.z, 1.0f);
+                        }
+                        if (F.out_depth) F.out_depth[out] = 0.0f;
+                    }
+                }
+            }
+            next += want < avail ? want : avail;
+        }
+        if (busy && !walking) {  // start sample s
+            f3 ro, rd;
+            iow_camera_ray(S, F, sx, sy, dsx, dsy, (int)s, ro, rd);
+            K.size = 0;
+            K.wmask = K.rmask = 0u;
+            skip = 0;
+            col = f3{0, 0, 0};
+            K.push(ro, rd, 1.0f, 1.0f, 0, c);
+            walking = true;
+        }
+        if (__ballot(busy) == 0) {
+            if (drained) break;
+            continue;
+        }
+        if (walking) {
+            iow_segment<false, Cfg::BS, Cfg::NS>(S, Fs, K, skip, col, (int)s, c, bstk, nodes);
+            if (K.size == 0) {  // sample done: out_Pixel's sum, and the even samples' beside it
+                fc = fc + col;
+                if ((s & 1u) == 0) ev = ev + col;
+                s++;
+                walking = false;
+                if (s >= s1) {
+                    state[2 * (size_t)out] = make_float4(fc.x, fc.y, fc.z, 0.0f);
+                    state[2 * (size_t)out + 1] = make_float4(K.at(0, 7), K.at(1, 7), K.at(2, 7), K.at(3, 7));
+                    aux[out] = make_float4(ev.x, ev.y, ev.z, __uint_as_float(s));
+                    if (F.out_rgba) {
+                        const f3 v = fc * rcp((float)s);
+                        reinterpret_cast<float4 *>(F.out_rgba)[out] = make_float4(v.x, v.y, v.z, 1.0f);
+                    }
+                    if (F.out_depth) F.out_depth[out] = 0.0f;
+                    busy = false;
+                }
+            }
+        }
+    }
+    flush(F, c);
+}
+
+// ------------------------------------------------------------------------------------------ select
+// What the three select kernels share.  The error of a pixel with n samples: a = acc * RN(1 / n),
+// e = even * RN(1 / ceil(n / 2)), err = (|a.x - e.x| + |a.y - e.y|) + |a.z - e.z| in binary32, +inf for
+// n < 2; the pixel is active iff n < stop and (n < min_samples or not err <= tol): a NaN keeps sampling.
+struct Select {
+    const float4 *state, *aux;
+    float tol;
+    uint32_t min_samples, stop;
+};
+__device__ __forceinline__ bool select_active(const Select &Q, size_t o, float &err) {
+    const float4 x = Q.aux[o];
+    const uint32_t n = __float_as_uint(x.w);
+    err = __builtin_inff();
+    if (n >= 2) {
+        const float4 s = Q.state[2 * o];
+        const float in = rcp((float)n), ih = rcp((float)((n + 1u) / 2u));
+        const f3 a = f3{s.x, s.y, s.z} * in, e = f3{x.x, x.y, x.z} * ih;
+        err = (__builtin_fabsf(a.x - e.x) + __builtin_fabsf(a.y - e.y)) + __builtin_fabsf(a.z - e.z);
+    }
+    return n < Q.stop && (n < Q.min_samples || !(err <= Q.tol));
+}
+// the rectangle of a frame for unit_pixel, everything else 0
+__device__ __forceinline__ void select_frame(Frame &F, const Frame &in) {
+    F.W = in.W; F.H = in.H;
+    F.x0 = in.x0; F.y0 = in.y0; F.tw = in.tw; F.th = in.th;
+}
+
+constexpr int kSelWaves = kBlock / 64;
+
+// 1: a lane per unit, a block's (active, inactive) counts into part[block]; the error image.
+__global__ __launch_bounds__(kBlock)
+void k_select_count(Frame Fin, Select Q, uint32_t n_units, uint2 *__restrict__ part, float *__restrict__ d_err) {
+    __shared__ uint2 s_cnt[kSelWaves];
+    Frame F{};
+    select_frame(F, Fin);
+    const uint32_t u = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+    bool in = false, act = false;
+    if (u < n_units) {
+        const UnitPix p = unit_pixel(F, u);
+        if (p.in_image) {
+            float err;
+            in = true;
+            act = select_active(Q, p.out, err);
+            if (d_err) d_err[p.out] = err;
+        }
+    }
+    const uint32_t na = (uint32_t)__popcll(__ballot(act)), ni = (uint32_t)__popcll(__ballot(in && !act));
+    if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = make_uint2(na, ni);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint2 t = make_uint2(0u, 0u);
+        for (int w = 0; w < kSelWaves; w++) { t.x += s_cnt[w].x; t.y += s_cnt[w].y; }
+        part[blockIdx.x] = t;
+    }
+}
+
+// 2: one block: part[0 .. n) becomes its exclusive scan, part[n] the totals, *n_active the active total.
+__global__ __launch_bounds__(kBlock)
+void k_select_scan(uint2 *__restrict__ part, uint32_t n, uint32_t *__restrict__ n_active) {
+    __shared__ uint2 s_sum[kSelWaves];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint2 carry = make_uint2(0u, 0u);  // the totals of the rounds before (block-uniform)
+    for (uint32_t base = 0; base < n; base += (uint32_t)kBlock) {
+        const uint32_t i = base + threadIdx.x;
+        const uint2 v = i < n ? part[i] : make_uint2(0u, 0u);
+        uint2 inc = v;  // inclusive scan over the wave
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t ax = __shfl_up(inc.x, d, 64), ay = __shfl_up(inc.y, d, 64);
+            if (lane >= (uint32_t)d) { inc.x += ax; inc.y += ay; }
+        }
+        if (lane == 63u) s_sum[wave] = inc;
+        __syncthreads();
+        uint2 off = carry, tot = carry;
+        for (uint32_t w = 0; w < (uint32_t)kSelWaves; w++) {
+            if (w < wave) { off.x += s_sum[w].x; off.y += s_sum[w].y; }
+            tot.x += s_sum[w].x; tot.y += s_sum[w].y;
+        }
+        if (i < n) part[i] = make_uint2(off.x + inc.x - v.x, off.y + inc.y - v.y);
+        carry = tot;
+        __syncthreads();  // s_sum is rewritten by the next round
+    }
+    if (threadIdx.x == 0) {
+        part[n] = carry;
+        *n_active = carry.x;
+    }
+}
+
+// 3: the scatter: an active unit's pixel at its active rank, an inactive one's {-1, -1} at the active
+// total + its inactive rank (so the list's tail, up to the rectangle's pixel count, is padding).
+__global__ __launch_bounds__(kBlock)
+void k_select_scatter(Frame Fin, Select Q, uint32_t n_units, uint32_t n_blocks, const uint2 *__restrict__ part,
+                      int2 *__restrict__ list) {
+    __shared__ uint2 s_cnt[kSelWaves];
+    Frame F{};
+    select_frame(F, Fin);
+    const uint32_t u = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+    bool in = false, act = false;
+    int2 px = make_int2(-1, -1);
+    if (u < n_units) {
+        const UnitPix p = unit_pixel(F, u);
+        if (p.in_image) {
+            float err;
+            in = true;
+            act = select_active(Q, p.out, err);
+            px = make_int2(p.x, p.y);
+        }
+    }
+    const unsigned long long ma = __ballot(act), mi = __ballot(in && !act);
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) s_cnt[wave] = make_uint2((uint32_t)__popcll(ma), (uint32_t)__popcll(mi));
+    __syncthreads();
+    uint2 off = part[blockIdx.x];
+    for (uint32_t w = 0; w < (uint32_t)kSelWaves; w++)
+        if (w < wave) { off.x += s_cnt[w].x; off.y += s_cnt[w].y; }
+    const uint32_t total = part[n_blocks].x;
+    if (act) list[off.x + lanes_below(ma)] = px;
+    else if (in) list[total + off.y + lanes_below(mi)] = make_int2(-1, -1);
+}
+
+// ------------------------------------------------------------------------------------------ launch
+constexpr uint32_t kAdaptRounds = 16;  // entries per claim: at most 16 x 64 (k_iow_pass's rule)
+
+namespace {
+int g_chunk_cap = 0;  // rt_debug_adaptive_chunk: 0 = none
+
+template <class Kn>
+hipError_t adapt_info(Kn kernel, int info[4]) {
+    hipFuncAttributes a;
+    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(kernel));
+    if (e != hipSuccess) return e;
+    info[0] = a.numRegs;
+    info[1] = (int)a.localSizeBytes;
+    info[2] = (int)a.sharedSizeBytes;
+    info[3] = occupancy_of(kernel, kBlock);
+    return hipSuccess;
+}
+// resident blocks per CU of the instance a scene runs, asked once each
+int iow_adapt_blocks(bool ln) {
+    static const int nb[2] = {occupancy_of(k_iow_adapt<false>, kBlock), occupancy_of(k_iow_adapt<true>, kBlock)};
+    return nb[ln ? 1 : 0];
+}
+dim3 lanes_grid(uint32_t n) { return dim3((n + (uint32_t)kBlock - 1u) / (uint32_t)kBlock); }
+}  // namespace
+
+hipError_t adaptive_kernel_info(int which, int info[4]) {
+    switch (which) {
+        case 0: return adapt_info(k_adapt_rays, info);
+        case 1: return adapt_info(k_adapt_fold, info);
+        case 2: return adapt_info(k_iow_adapt<true>, info);
+        case 3: return adapt_info(k_iow_adapt<false>, info);
+        case 4: return adapt_info(k_select_count, info);
+        case 5: return adapt_info(k_select_scan, info);
+        case 6: return adapt_info(k_select_scatter, info);
+    }
+    return hipErrorInvalidValue;
+}
+
+int adaptive_chunk_cap_now() { return g_chunk_cap; }
+
+int adaptive_chunk_cap(int samples) {
+    const int prev = g_chunk_cap;
+    g_chunk_cap = samples > 0 ? samples : 0;
+    return prev;
+}
+
+hipError_t launch_adapt_rays(const Frame &f, const InwScene &sc, const int2 *pixels, uint32_t n_pixels,
+                             const float4 *aux, uint32_t stop, uint32_t ns, float4 *rays, hipStream_t s) {
+    const uint32_t n = n_pixels * ns;  // <= 2^31 (the caller's chunks)
+    hipLaunchKernelGGL(k_adapt_rays, lanes_grid(n), dim3(kBlock), 0, s, f, sc, pixels, aux, stop, ns, n, rays);
+    return hipGetLastError();
+}
+
+hipError_t launch_adapt_fold(const Frame &f, const int2 *pixels, uint32_t n_pixels, uint32_t stop, uint32_t ns,
+                             bool last, const float4 *out, float4 *state, float4 *aux, hipStream_t s) {
+    hipLaunchKernelGGL(k_adapt_fold, lanes_grid(n_pixels), dim3(kBlock), 0, s, f, pixels, n_pixels, stop, ns,
+                       last ? 1u : 0u, out, state, aux);
+    return hipGetLastError();
+}
+
+hipError_t launch_iow_adapt(const Frame &f, const IowScene &sc, const int2 *pixels, uint32_t n_pixels, uint32_t stop,
+                            uint32_t ns, float4 *state, float4 *aux, unsigned *queue, int cus, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(queue, 0, sizeof(unsigned), s);
+    if (e != hipSuccess) return e;
+    const bool ln = iow_lds(sc);
+    // the grid and the claim size: every wave of the grid gets at least four claims (k_iow_pass's rule)
+    const uint32_t need = (n_pixels + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
+    uint32_t cap = (uint32_t)(cus > 0 ? cus : 1) * (uint32_t)iow_adapt_blocks(ln);
+    const int max_blocks = pass_max_blocks_now();
+    if (max_blocks > 0 && (uint32_t)max_blocks < cap) cap = (uint32_t)max_blocks;
+    const dim3 g(need < cap ? need : cap), b(kBlock);
+    const uint32_t per_wave = n_pixels / (64u * g.x * (uint32_t)(kBlock / 64) * 4u);
+    const uint32_t rounds = per_wave < 1u ? 1u : (per_wave > kAdaptRounds ? kAdaptRounds : per_wave);
+    if (ln) hipLaunchKernelGGL((k_iow_adapt<true>), g, b, 0, s, f, sc, pixels, stop, ns, state, aux, queue, rounds, n_pixels);
+    else hipLaunchKernelGGL((k_iow_adapt<false>), g, b, 0, s, f, sc, pixels, stop, ns, state, aux, queue, rounds, n_pixels);
+    return hipGetLastError();
+}
+
+uint32_t select_blocks(const Frame &f) { return (units_of(f) + (uint32_t)kBlock - 1u) / (uint32_t)kBlock; }
+
+hipError_t launch_pass_select(const Frame &f, const float4 *state, const float4 *aux, float tol, uint32_t min_samples,
+                              uint32_t stop, int2 *list, uint32_t *n_active, float *err, uint2 *part, hipStream_t s) {
+    const uint32_t n_units = units_of(f), n_blocks = select_blocks(f);
+    const Select q{state, aux, tol, min_samples, stop};
+    const dim3 g(n_blocks), b(kBlock);
+    hipLaunchKernelGGL(k_select_count, g, b, 0, s, f, q, n_units, part, err);
+    hipLaunchKernelGGL(k_select_scan, dim3(1), b, 0, s, part, n_blocks, n_active);
+    hipLaunchKernelGGL(k_select_scatter, g, b, 0, s, f, q, n_units, n_blocks, part, list);
+    return hipGetLastError();
+}
+
+}  // namespace rtk

@@ -218,6 +218,85 @@ int passes_blocking(const rt_camera *cam, const rt_params *p, const uint32_t *cu
     return st ? read_stats(d_ctr.p, ms, st) : RT_OK;
 }
 
+// The blocking adaptive passes: a temporary scene from make(scene), the host buffers up (pixels outside the
+// rectangle keep their bytes), the aux buffer zeroed and every pixel of the rectangle listed (a select that
+// finds every pixel active), then rounds of one listed pass of `batch` samples and one select, with the
+// active count read back, while pixels are active and rounds remain (max_rounds == 0: no limit).  The
+// rounds are timed on the null stream and summed.
+template <class Make>
+int adaptive_blocking(const rt_camera *cam, const rt_params *p, uint32_t batch, float tol, uint32_t min_samples,
+                      uint32_t max_rounds, float *rgba, float *depth, uint32_t *count, float *err,
+                      rt_pass_state *state_out, rt_pass_aux *aux_out, uint32_t *rounds_out, int device, rt_stats *st,
+                      Make &&make) {
+    int rc = check_device(device);
+    if (rc != RT_OK) return rc;
+    std::unique_ptr<rt_dev_scene> s = temp_scene();
+    if (!s) return RT_E_ARG;
+    try {  // the host builders allocate: no exception crosses the ABI
+        rc = make(s.get());
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    if (rc != RT_OK) return rc;
+    if (st) std::memset(st, 0, sizeof(*st));
+    if (rounds_out) *rounds_out = 0;
+    const size_t npx = size_t(p->width) * size_t(p->height);
+    const rtk::Frame f = make_frame(cam, p);
+    const size_t cap = size_t(f.tw > 0 ? f.tw : 0) * size_t(f.th > 0 ? f.th : 0);  // the list's capacity
+    DevBuf d_state, d_aux, d_rgba, d_depth, d_err, d_list, d_n, d_ctr;
+    if (state_out) HIP_OK(d_state.upload(state_out, npx * sizeof(rt_pass_state)));
+    else HIP_OK(d_state.alloc(npx * sizeof(rt_pass_state)));
+    HIP_OK(d_aux.alloc(npx * sizeof(rt_pass_aux)));
+    HIP_OK(hipMemset(d_aux.p, 0, npx * sizeof(rt_pass_aux)));
+    HIP_OK(d_rgba.upload(rgba, npx * 16));
+    if (depth) HIP_OK(d_depth.upload(depth, npx * 4));
+    if (err) HIP_OK(d_err.upload(err, npx * 4));
+    HIP_OK(d_list.alloc(cap * sizeof(rt_pixel)));
+    HIP_OK(d_n.alloc(sizeof(uint32_t)));
+    HIP_OK(d_ctr.alloc(6 * sizeof(unsigned long long)));
+    HIP_OK(hipMemset(d_ctr.p, 0, 6 * sizeof(unsigned long long)));
+    auto select = [&](float t, uint32_t m, float *e, uint32_t *n_active) -> int {
+        const int r = rt_pass_select_async(s.get(), p, d_state.as<rt_pass_state>(), d_aux.as<rt_pass_aux>(), t, m,
+                                           d_list.as<rt_pixel>(), d_n.as<uint32_t>(), e, nullptr);
+        if (r != RT_OK) return r;
+        HIP_OK(hipMemcpy(n_active, d_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return int(RT_OK);
+    };
+    uint32_t n_active = 0, rounds = 0;
+    if ((rc = select(-1.0f, 0, nullptr, &n_active)) != RT_OK) return rc;  // every pixel has 0 samples: all active
+    double total_ms = 0.0;
+    while (n_active > 0 && (max_rounds == 0 || rounds < max_rounds)) {
+        double ms = 0.0;
+        rc = timed([&]() -> int {
+            const int r = rt_render_pass_pixels_async(s.get(), cam, p, d_list.as<rt_pixel>(), n_active, batch,
+                                                      d_state.as<rt_pass_state>(), d_aux.as<rt_pass_aux>(),
+                                                      d_rgba.as<float>(), depth ? d_depth.as<float>() : nullptr,
+                                                      d_ctr.as<uint64_t>(), nullptr);
+            return r != RT_OK ? r : select(tol, min_samples, err ? d_err.as<float>() : nullptr, &n_active);
+        }, &ms);
+        if (rc != RT_OK) return rc;
+        total_ms += ms;
+        rounds++;
+    }
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(rgba, d_rgba.p, npx * 16, hipMemcpyDeviceToHost));
+    if (depth) HIP_OK(hipMemcpy(depth, d_depth.p, npx * 4, hipMemcpyDeviceToHost));
+    if (err) HIP_OK(hipMemcpy(err, d_err.p, npx * 4, hipMemcpyDeviceToHost));
+    if (state_out) HIP_OK(hipMemcpy(state_out, d_state.p, npx * sizeof(rt_pass_state), hipMemcpyDeviceToHost));
+    if (count || aux_out) {  // the rectangle's pixels of the aux buffer (the others were never the frame's)
+        std::vector<rt_pass_aux> aux(npx);
+        HIP_OK(hipMemcpy(aux.data(), d_aux.p, npx * sizeof(rt_pass_aux), hipMemcpyDeviceToHost));
+        for (int y = std::max(f.y0, 0); y < std::min(f.y0 + f.th, f.H); y++)
+            for (int x = std::max(f.x0, 0); x < std::min(f.x0 + f.tw, f.W); x++) {
+                const size_t i = size_t(y) * size_t(f.W) + size_t(x);
+                if (count) count[i] = aux[i].count;
+                if (aux_out) aux_out[i] = aux[i];
+            }
+    }
+    if (rounds_out) *rounds_out = rounds;
+    return st ? read_stats(d_ctr.p, total_ms, st) : RT_OK;
+}
+
 }  // namespace
 
 rt_options g_opt = default_options();
@@ -888,6 +967,106 @@ int rt_render_passes_iow03(const float *types, const float *records, uint32_t n,
     if (p->show_normal) return RT_E_UNSUPPORTED;
     return passes_blocking(cam, p, cuts, n_cuts, rgba, nullptr, state_out, device, st,
                            [&](rt_dev_scene *s) { return make_iow03(s, types, records, n, p->spp); });
+}
+
+// ------------------------------------------------------------------------ adaptive sample passes
+int rt_render_pass_pixels_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p, const rt_pixel *d_pixels,
+                                uint32_t n_pixels, uint32_t ns, rt_pass_state *d_state, rt_pass_aux *d_aux,
+                                float *d_rgba, float *d_depth, uint64_t *d_counters, void *stream) {
+    static_assert(sizeof(rt_pass_aux) == 16, "rt_pass_aux is a float4");
+    if (!s || !cam || !params_ok(p) || !d_state || !d_aux || p->spp != s->spp || s->broken) return RT_E_ARG;
+    if (n_pixels > (1u << 31) || (n_pixels > 0 && !d_pixels)) return RT_E_ARG;
+    if (p->show_normal) return RT_E_UNSUPPORTED;  // one normal per sample, no fold state
+    if (n_pixels == 0 || ns == 0) return RT_OK;
+    const bool iow = s->kind == 3;
+    const uint32_t stop = uint32_t(iow ? s->s_stop : s->spp);  // rt_render_pass_async's S
+    ns = std::min(ns, stop);                                    // no pixel has more samples left
+    rt_params whole = *p;
+    whole.tile_w = whole.tile_h = 0;  // the list says which pixels
+    rtk::Frame f = make_frame(cam, &whole);
+    f.out_rgba = d_rgba; f.out_depth = d_depth;
+    f.counters = reinterpret_cast<unsigned long long *>(d_counters);
+    f.dbg = nullptr; f.px_rays = nullptr;  // the renders' diagnostics hooks do not apply
+    f.leaf_batch = s->opt.iow_leaf_batch;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    float4 *state = reinterpret_cast<float4 *>(d_state), *aux = reinterpret_cast<float4 *>(d_aux);
+    const int2 *px = reinterpret_cast<const int2 *>(d_pixels);
+    if (iow) {
+        unsigned *queue = s->counter.as<unsigned>() + 192;  // the passes' own: calls on one scene do not overlap
+        const hipError_t e = rtk::launch_iow_adapt(f, iow_view(*s), px, n_pixels, stop, ns, state, aux, queue, s->cus, st);
+        return e == hipSuccess ? RT_OK : launch_failed(e);
+    }
+    // INW: rt_render_pass_async's chunks, driven by the list: n_pixels * chunk records of rays and answers in
+    // the scene's pass workspace; every chunk's fold advances the counts the next chunk's rays start from.
+    constexpr uint64_t kPassRecords = uint64_t(1) << 25;
+    uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(ns, kPassRecords / n_pixels)));
+    const int cap_chunk = rtk::adaptive_chunk_cap_now();  // rt_debug_adaptive_chunk
+    if (cap_chunk > 0) chunk = std::min(chunk, uint32_t(cap_chunk));
+    HIP_OK(s->pass_ws.reserve(size_t(n_pixels) * chunk * 2 * sizeof(rt_path_ray)));
+    float4 *rays = s->pass_ws.as<float4>(), *out = rays + size_t(n_pixels) * chunk * 2;
+    rtk::InwScene sc = inw_view(*s);
+    if (s->layout == 4) sc.sph = nullptr;
+    sc.fused = (s->opt.inw_fused_cull && sc.wnodes && s->walk.wbound <= 1000.0f) ? 1 : 0;
+    // the frame's child order: dot(dir, (1, 1, 1)) > 0 in binary32, the shader's order (inw_segment)
+    const float dsum = (cam->dir[0] * 1.0f + cam->dir[1] * 1.0f) + cam->dir[2] * 1.0f;
+    unsigned *queue = s->counter.as<unsigned>() + 224;
+    const int cap = rtk::inw_paths_max_blocks(rtk::pass_max_blocks_now());  // rt_debug_pass_max_blocks caps the paths' grid
+    hipError_t e = hipSuccess;
+    for (uint32_t c0 = 0; c0 < ns && e == hipSuccess; c0 += chunk) {
+        const uint32_t nsc = std::min(chunk, ns - c0);
+        e = rtk::launch_adapt_rays(f, sc, px, n_pixels, aux, stop, nsc, rays, st);
+        if (e == hipSuccess)
+            e = rtk::launch_inw_paths(sc, rays, n_pixels * nsc, s->spp, p->max_bounces, dsum > 0.0f, out,
+                                      reinterpret_cast<unsigned long long *>(d_counters), queue, s->cus, st);
+        if (e == hipSuccess) e = rtk::launch_adapt_fold(f, px, n_pixels, stop, nsc, c0 + nsc == ns, out, state, aux, st);
+    }
+    (void)rtk::inw_paths_max_blocks(cap);
+    return e == hipSuccess ? RT_OK : launch_failed(e);
+}
+
+int rt_pass_select_async(rt_dev_scene *s, const rt_params *p, const rt_pass_state *d_state, const rt_pass_aux *d_aux,
+                         float tol, uint32_t min_samples, rt_pixel *d_list, uint32_t *d_n_active, float *d_err,
+                         void *stream) {
+    if (!s || !params_ok(p) || !d_state || !d_aux || !d_list || !d_n_active || p->spp != s->spp || s->broken)
+        return RT_E_ARG;
+    const rtk::Frame f = make_frame(nullptr, p);
+    const uint32_t units = rtk::units_of(f);
+    if (units == 0 || units > (1u << 31)) return RT_E_ARG;
+    HIP_OK(s->select_ws.reserve((size_t(rtk::select_blocks(f)) + 1) * sizeof(uint2)));
+    const uint32_t stop = uint32_t(s->kind == 3 ? s->s_stop : s->spp);
+    const hipError_t e = rtk::launch_pass_select(f, reinterpret_cast<const float4 *>(d_state),
+                                                 reinterpret_cast<const float4 *>(d_aux), tol, min_samples, stop,
+                                                 reinterpret_cast<int2 *>(d_list), d_n_active, d_err,
+                                                 s->select_ws.as<uint2>(), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RT_OK : launch_failed(e);
+}
+
+int rt_render_adaptive_inw(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                           uint32_t n_lights, const rt_texture *tex, int n_tex, const rt_camera *cam, const rt_params *p,
+                           uint32_t batch, float tol, uint32_t min_samples, uint32_t max_rounds, float *rgba,
+                           float *depth, uint32_t *count, float *err, rt_pass_state *state_out, rt_pass_aux *aux_out,
+                           uint32_t *rounds_out, int device, rt_stats *st) {
+    if (!geom || !nodes || n == 0 || (layout != 1 && layout != 4) || !cam || !params_ok(p) || !rgba || batch == 0)
+        return RT_E_ARG;
+    if (layout == 4 && n_lights > 0 && !lights) return RT_E_ARG;
+    if (!textures_ok(tex, n_tex)) return RT_E_ARG;
+    if (n_tex == 0 && inw_textured(geom, n, layout)) return RT_E_UNSUPPORTED;  // no texture bound
+    if (p->show_normal) return RT_E_UNSUPPORTED;
+    return adaptive_blocking(cam, p, batch, tol, min_samples, max_rounds, rgba, depth, count, err, state_out, aux_out,
+                             rounds_out, device, st, [&](rt_dev_scene *s) {
+        return make_inw(s, geom, n, layout, nodes, lights, n_lights, tex, n_tex, p->spp);
+    });
+}
+
+int rt_render_adaptive_iow03(const float *types, const float *records, uint32_t n, const rt_camera *cam,
+                             const rt_params *p, uint32_t batch, float tol, uint32_t min_samples, uint32_t max_rounds,
+                             float *rgba, uint32_t *count, float *err, rt_pass_state *state_out, rt_pass_aux *aux_out,
+                             uint32_t *rounds_out, int device, rt_stats *st) {
+    if (!types || !records || n == 0 || !cam || !params_ok(p) || !rgba || batch == 0) return RT_E_ARG;
+    if (p->show_normal) return RT_E_UNSUPPORTED;
+    return adaptive_blocking(cam, p, batch, tol, min_samples, max_rounds, rgba, nullptr, count, err, state_out,
+                             aux_out, rounds_out, device, st,
+                             [&](rt_dev_scene *s) { return make_iow03(s, types, records, n, p->spp); });
 }
 
 // ------------------------------------------------------------------------ rt_scene.h

@@ -530,11 +530,14 @@ int rt_debug_pixels_kernel(int which, int info[4]) {
 }
 
 int rt_debug_pass_kernel(int which, int info[4]) {
-    if (!info || which < 0 || which > 3) return RT_E_ARG;
-    HIP_OK(rtk::pass_kernel_info(which, info));
+    if (!info || which < 0 || (which > 3 && which < 8) || which > 14) return RT_E_ARG;
+    if (which >= 8) HIP_OK(rtk::adaptive_kernel_info(which - 8, info));  // rt_adaptive.hip's
+    else HIP_OK(rtk::pass_kernel_info(which, info));
     return RT_OK;
 }
 
 int rt_debug_pass_max_blocks(int blocks) { return rtk::pass_max_blocks(blocks); }
+
+int rt_debug_adaptive_chunk(int samples) { return rtk::adaptive_chunk_cap(samples); }
 
 }  // extern "C"

@@ -159,6 +159,7 @@ struct rt_dev_scene {
     DevBuf tex, tex_info;  // INW-04 material textures (float4 texels, (first, w, h, 0) per texture)
     uint32_t n_tex = 0;
     DevBuf pass_ws;        // INW progressive passes: the camera rays and answers of one chunk of samples
+    DevBuf select_ws;      // rt_pass_select_async: the block partials of the rectangle's units (8 B a block)
     DevBuf walk_ctr;       // the last frame's closest-hit queries handed to the LBVH walks (u64)
     bool broken = false;   // a failed rt_dev_scene_inw_update / rt_dev_scene_iow03_update left the buffers
                            // inconsistent: no renders, no queries

@@ -496,6 +496,32 @@ hipError_t launch_pass_fold(const Frame &f, uint32_t s0, uint32_t ns, uint32_t k
 hipError_t pass_kernel_info(int which, int info[4]);
 int pass_max_blocks_now();        // the cap rt_debug_pass_max_blocks set (0 = none)
 int pass_max_blocks(int blocks);  // rt_debug_pass_max_blocks: cap the grid (0 = off); the previous cap
+// rt_adaptive.hip: a pass over the list `pixels` (x, y pairs; an entry outside the image is skipped) in
+// which every pixel renders samples [count, min(count + ns, stop)), count = its rt_pass_aux's (aux: one
+// float4 per pixel of the W x H image: even.xyz, the count's bits).
+// INW: the two ends of a chunk around launch_inw_paths.  Record k * ns + j = entry k, sample count + j
+// (the invalid sample past stop; n_pixels * ns <= 2^31 records of 2 float4); and the fold of the answers
+// into state and aux, which advances the count, with the image acc * RN(1 / count) and the depth written
+// when `last`.
+hipError_t launch_adapt_rays(const Frame &f, const InwScene &sc, const int2 *pixels, uint32_t n_pixels,
+                             const float4 *aux, uint32_t stop, uint32_t ns, float4 *rays, hipStream_t s);
+hipError_t launch_adapt_fold(const Frame &f, const int2 *pixels, uint32_t n_pixels, uint32_t stop, uint32_t ns,
+                             bool last, const float4 *out, float4 *state, float4 *aux, hipStream_t s);
+// IOW-03: launch_iow_pass's persistent grid over the list (queue: one u32, zeroed here; pass_max_blocks caps
+// the grid).
+hipError_t launch_iow_adapt(const Frame &f, const IowScene &sc, const int2 *pixels, uint32_t n_pixels, uint32_t stop,
+                            uint32_t ns, float4 *state, float4 *aux, unsigned *queue, int cus, hipStream_t s);
+// The stable partition of the units of f's rectangle into the active pixels, in unit order, and a tail of
+// {-1, -1} up to the rectangle's pixel count; *n_active = the active count; err (W x H, may be null): the
+// estimate of the rectangle's pixels.  part: select_blocks(f) + 1 uint2 of scratch.  Three launches.
+uint32_t select_blocks(const Frame &f);
+hipError_t launch_pass_select(const Frame &f, const float4 *state, const float4 *aux, float tol, uint32_t min_samples,
+                              uint32_t stop, int2 *list, uint32_t *n_active, float *err, uint2 *part, hipStream_t s);
+// {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of k_adapt_rays (which = 0), k_adapt_fold
+// (1), k_iow_adapt (2 nodes staged in LDS, 3 not), k_select_count (4), k_select_scan (5), k_select_scatter (6)
+hipError_t adaptive_kernel_info(int which, int info[4]);
+int adaptive_chunk_cap_now();          // the cap rt_debug_adaptive_chunk set (0 = none)
+int adaptive_chunk_cap(int samples);   // rt_debug_adaptive_chunk: cap an INW chunk's samples (0 = off); the previous cap
 // The persistent render kernels, by name, and the resident blocks per CU of each (occupancy query;
 // 2 if it fails).  The kernels are private to their units, so resident_blocks_per_cu
 // (rt_iow_render.hip) asks the unit that owns the kernel.

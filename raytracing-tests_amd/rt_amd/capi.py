@@ -246,6 +246,19 @@ SIGNATURES = {
                                          C.c_int, _FP, C.c_void_p, C.c_int, C.POINTER(RtStats)]),
     "rt_debug_pass_kernel": (C.c_int, [C.c_int, _IP]),
     "rt_debug_pass_max_blocks": (C.c_int, [C.c_int]),
+    "rt_render_pass_pixels_async": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_void_p,
+                                              C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "rt_pass_select_async": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.c_void_p, C.c_void_p, C.c_float, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_adaptive_inw": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtTexture), C.c_int,
+                                         C.POINTER(RtCamera), C.POINTER(RtParams), C.c_uint32, C.c_float, C.c_uint32,
+                                         C.c_uint32, _FP, _FP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int, C.POINTER(RtStats)]),
+    "rt_render_adaptive_iow03": (C.c_int, [_FP, _FP, C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_uint32,
+                                           C.c_float, C.c_uint32, C.c_uint32, _FP, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RtStats)]),
+    "rt_debug_adaptive_chunk": (C.c_int, [C.c_int]),
     "rt_render_multi_async": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
@@ -977,10 +990,84 @@ PASS_KERNELS = ("k_pass_rays (INW)", "k_pass_fold (INW)", "k_iow_pass LDS nodes"
 
 
 def pass_kernel_info(which: int) -> dict:
-    """rt_debug_pass_kernel: registers, scratch, LDS and resident blocks per CU of PASS_KERNELS[which]."""
+    """rt_debug_pass_kernel: registers, scratch, LDS and resident blocks per CU of PASS_KERNELS[which]
+    (which = 0..3) or ADAPTIVE_KERNELS[which] (8..14)."""
     info = (C.c_int * 4)()
     check(load().rt_debug_pass_kernel(int(which), info), "rt_debug_pass_kernel")
     return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
+
+
+# ------------------------------------------------------------- adaptive sample passes
+# rt_pass_aux (include/rt_hip.h), 16 bytes; rt_pixel, 8 bytes
+PASS_AUX_DTYPE = np.dtype([("even", np.float32, 3), ("count", np.uint32)])
+PIXEL_DTYPE = np.dtype([("x", np.int32), ("y", np.int32)])
+# rt_debug_pass_kernel's `which` of the adaptive-pass kernels
+ADAPTIVE_KERNELS = {8: "k_adapt_rays (INW)", 9: "k_adapt_fold (INW)", 10: "k_iow_adapt LDS nodes",
+                    11: "k_iow_adapt global nodes", 12: "k_select_count", 13: "k_select_scan", 14: "k_select_scatter"}
+
+
+def _dptr(t):
+    """A device pointer: None, an integer, or anything with data_ptr() (a torch tensor)."""
+    return t.data_ptr() if hasattr(t, "data_ptr") else t
+
+
+def pass_pixels(handle, camera: RtCamera, params: RtParams, d_pixels, n_pixels: int, ns: int, d_state, d_aux,
+                d_rgba=None, d_depth=None, d_counters=None, stream=None) -> int:
+    """rt_render_pass_pixels_async on device buffers (pointers or torch tensors); returns the status."""
+    return load().rt_render_pass_pixels_async(handle, C.byref(camera), C.byref(params), _dptr(d_pixels), n_pixels, ns,
+                                              _dptr(d_state), _dptr(d_aux), _dptr(d_rgba), _dptr(d_depth),
+                                              _dptr(d_counters), stream)
+
+
+def pass_select(handle, params: RtParams, d_state, d_aux, tol: float, min_samples: int, d_list, d_n_active,
+                d_err=None, stream=None) -> int:
+    """rt_pass_select_async on device buffers (pointers or torch tensors); returns the status."""
+    return load().rt_pass_select_async(handle, C.byref(params), _dptr(d_state), _dptr(d_aux), float(tol),
+                                       int(min_samples), _dptr(d_list), _dptr(d_n_active), _dptr(d_err), stream)
+
+
+def render_adaptive(sc: Scene, batch: int, tol: float, min_samples: int = 2, max_rounds: int | None = None,
+                    params: RtParams | None = None, rgba=None, depth=None, state=None, device: int = -1) -> dict:
+    """rt_render_adaptive_inw / rt_render_adaptive_iow03: the blocking adaptive loop on the frame (sc.camera,
+    params) -- rounds of one listed pass of `batch` samples and one select, while pixels are active and
+    rounds remain (max_rounds None: no limit).  Returns {"rgba": (H, W, 4), "depth": (H, W) or None on
+    IOW-03, "count": (H, W) uint32, "err": (H, W) (+inf where no select ran), "state": (H, W)
+    PASS_STATE_DTYPE, "aux": (H, W) PASS_AUX_DTYPE, "rounds": int, "stats": dict}.  rgba, depth and state:
+    arrays of those shapes to start from (pixels outside the rectangle keep their bytes); default zeros."""
+    lib = load()
+    p = params or sc.params
+    iow = sc.stage == RT_STAGE_IOW03
+    H, W = p.height, p.width
+    rgba = np.zeros((H, W, 4), np.float32) if rgba is None else np.ascontiguousarray(rgba, np.float32)
+    assert rgba.shape == (H, W, 4)
+    if iow:
+        depth = None
+    else:
+        depth = np.zeros((H, W), np.float32) if depth is None else np.ascontiguousarray(depth, np.float32)
+        assert depth.shape == (H, W)
+    state = np.zeros((H, W), PASS_STATE_DTYPE) if state is None else np.ascontiguousarray(state, PASS_STATE_DTYPE)
+    assert state.shape == (H, W)
+    count = np.zeros((H, W), np.uint32)
+    err = np.full((H, W), np.inf, np.float32)
+    aux = np.zeros((H, W), PASS_AUX_DTYPE)
+    rounds = C.c_uint32(0)
+    st = RtStats()
+    mid = (int(batch), float(tol), int(min_samples), int(max_rounds or 0), fptr(rgba))
+    tail = (count.ctypes.data, err.ctypes.data, state.ctypes.data, aux.ctypes.data, C.addressof(rounds), device,
+            C.byref(st))
+    if iow:
+        check(lib.rt_render_adaptive_iow03(fptr(sc.types), fptr(sc.records), sc.n, C.byref(sc.camera), C.byref(p),
+                                           *mid, *tail), "rt_render_adaptive_iow03")
+    else:
+        lights = sc.lights if sc.lights is not None and len(sc.lights) else None
+        tex = getattr(sc, "textures", None) or []
+        arr, keep = texture_array(tex)
+        check(lib.rt_render_adaptive_inw(fptr(sc.geom), sc.n, sc.layout, fptr(sc.nodes), fptr(lights), sc.n_lights,
+                                         arr if tex else None, len(tex), C.byref(sc.camera), C.byref(p), *mid,
+                                         fptr(depth), *tail), "rt_render_adaptive_inw")
+        del keep
+    return {"rgba": rgba, "depth": depth, "count": count, "err": err, "state": state, "aux": aux,
+            "rounds": int(rounds.value), "stats": st.as_dict()}
 
 
 def render_iow01(camera: RtCamera, sphere, params: RtParams):
