@@ -13,33 +13,25 @@
 // the image), the unchanged path kernel answers them, k_adapt_fold folds an entry's answers in sample
 // order and advances its count, so the next chunk's rays start from the new count.
 // IOW-03: k_iow_adapt is k_iow_pass with the pixel, its first sample and its RI fields taken from the list
-// entry, the pixel's count and its state, and `even` folded beside the sum.  (k_iow_pass's loop is
-// repeated here, not shared through a header, so that kernel stays byte for byte what it was.)
+// entry, the pixel's count and its state, and `even` folded beside the sum: both run iow_pass_loop
+// (rt_pass_loop.hpp), this one with the list as its source.
+// Shared with rt_passes.hip through rt_pass_common.hpp: the frames, listed(), the INW record writer, the
+// fold's start from the state and the image write.  The INW folds' sample loops stay in their kernels: moved
+// into one function, k_adapt_fold's registers changed (29 SGPRs, or 40 VGPRs, against the pinned 27 / 39).
 // Select: a stable partition of the rectangle's units (unit_pixel's order) in three plain launches --
 // per-block counts, an exclusive scan of the block partials in one block, the scatter.  No block waits on
 // another block.
-#include "rt_render_common.hpp"
-#include "rt_pass_common.hpp"
-#include "rt_inw_shade.hpp"
-#include "rt_iow_shade.hpp"
+#include "rt_pass_loop.hpp"
 
 namespace rtk {
-
-// Waves per SIMD of k_iow_adapt: k_iow_pass's (bound by LDS: 2 blocks per CU with the nodes staged, 3 without)
-template <bool LN> constexpr int kAdaptIowWaves = LN ? 2 : 3;
-
-// A list entry: inside the image or skipped ({-1, -1} is rt_pass_select_async's padding).
-__device__ __forceinline__ bool listed(const Frame &F, int2 p) {
-    return p.x >= 0 && p.y >= 0 && p.x < F.W && p.y < F.H;
-}
 
 // rt_pass_aux as the kernels read it: (even.xyz, count bits)
 __device__ __forceinline__ uint32_t aux_count(const float4 *aux, size_t out) { return __float_as_uint(aux[out].w); }
 
 // ------------------------------------------------------------------------------------------ INW
-// One lane per record: record k * ns + j is the camera ray of sample count + j of entry k's pixel, by the
-// render's own sample start; the sample is 0xffffffff, which the path kernel answers without a path, past
-// `stop` or for an entry outside the image.  n = n_pixels * ns <= 2^31.
+// One lane per record: record k * ns + j is the camera ray of sample count + j of entry k's pixel
+// (pass_ray_record); the sample is the invalid one past `stop` or for an entry outside the image.
+// n = n_pixels * ns <= 2^31.
 __global__ __launch_bounds__(kBlock)
 void k_adapt_rays(Frame Fin, InwScene S, const int2 *__restrict__ pixels, const float4 *__restrict__ aux,
                   uint32_t stop, uint32_t ns, uint32_t n, float4 *__restrict__ rays) {
@@ -55,23 +47,15 @@ void k_adapt_rays(Frame Fin, InwScene S, const int2 *__restrict__ pixels, const 
         const uint32_t c = aux_count(aux, (size_t)p.y * F.W + p.x);
         if (c < stop && j < stop - c) s = c + j;
     }
-    if (s != 0xffffffffu) {
-        PassRay K;
-        Ctr c;
-        inw_start_sample(S, F, K, p.x, p.y, (int)s, c);
-        r[0] = make_float4(K.o.x, K.o.y, K.o.z, __uint_as_float(s));
-        r[1] = make_float4(K.d.x, K.d.y, K.d.z, 0.0f);
-    } else {
-        r[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xffffffffu));
-        r[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
+    if (s != 0xffffffffu) pass_ray_record(S, F, p.x, p.y, s, r);
+    else pass_no_record(r);
 }
 
 // One lane per entry: End() over the entry's answers of samples [c, min(c + ns, stop)) in sample order,
-// from the pixel's state and aux (the state is not read when c == 0: the first sample is assigned) --
-// sqrt(colour) added to acc and, at even samples, to even; the depth of sample spp / 2 -- and the state,
-// the aux and the new count back.  last: the chunk is the pass's last, and the image acc * RN(1 / count)
-// and the depth are written (also for an entry that had nothing left to render).
+// from the pixel's state (pass_fold_begin) and aux -- sqrt(colour) added to acc and, at even samples, to
+// even; the depth of sample spp / 2 -- and the state, the aux and the new count back.  last: the chunk is
+// the pass's last, and the image acc * RN(1 / count) and the depth are written (also for an entry that had
+// nothing left to render).
 __global__ __launch_bounds__(kBlock)
 void k_adapt_fold(Frame Fin, const int2 *__restrict__ pixels, uint32_t n_pixels, uint32_t stop, uint32_t ns,
                   uint32_t last, const float4 *__restrict__ out, float4 *__restrict__ state,
@@ -86,13 +70,9 @@ void k_adapt_fold(Frame Fin, const int2 *__restrict__ pixels, uint32_t n_pixels,
     const uint32_t mid = (uint32_t)F.spp / 2u;
     const float4 x = aux[o];
     const uint32_t c = __float_as_uint(x.w);
-    f3 acc = f3{0, 0, 0}, ev = f3{x.x, x.y, x.z};
-    float dmid = 0.0f;
-    if (c != 0) {
-        const float4 a = state[2 * o];
-        acc = f3{a.x, a.y, a.z};
-        dmid = a.w;
-    }
+    f3 acc, ev = f3{x.x, x.y, x.z};
+    float dmid;
+    pass_fold_begin(state, o, c, acc, dmid);
     const uint32_t m = c < stop ? (ns < stop - c ? ns : stop - c) : 0u;  // samples to fold
     const float4 *a = out + 2 * (size_t)k * ns;
     for (uint32_t j = 0; j < m; j++) {
@@ -109,130 +89,18 @@ void k_adapt_fold(Frame Fin, const int2 *__restrict__ pixels, uint32_t n_pixels,
         aux[o] = make_float4(ev.x, ev.y, ev.z, __uint_as_float(c1));
     }
     if (!last) return;
-    if (F.out_rgba) {
-        const f3 v = acc * rcp((float)c1);
-        reinterpret_cast<float4 *>(F.out_rgba)[o] = make_float4(v.x, v.y, v.z, 1.0f);
-    }
-    if (F.out_depth) F.out_depth[o] = dmid;
+    pass_write_image(F, o, acc, rcp((float)c1), dmid);
 }
 
 // ------------------------------------------------------------------------------------------ IOW-03
-// k_iow_pass over the list: a persistent grid, a lane owns one entry's pixel at a time, a wave claims
-// 64 * rounds consecutive entries with one atomic and hands them to its free lanes by ballot and mbcnt.
-// The lane's samples are [count, min(count + ns, stop)); an entry with nothing left has its image
-// rewritten from its state.
+// The shared loop over the list: a lane's samples are [count, min(count + ns, stop)); an entry with
+// nothing left has its image rewritten from its state.
 template <bool LN>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdaptIowWaves<LN>)))
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPassIowWaves<LN>)))
 void k_iow_adapt(Frame Fin, IowScene S, const int2 *__restrict__ pixels, uint32_t stop, uint32_t ns,
                  float4 *__restrict__ state, float4 *__restrict__ aux, unsigned *queue, uint32_t rounds,
                  uint32_t n_units) {
-    Frame F{}, Fs{};
-    pass_frame(F, Fin);
-    pass_seg_frame(Fs, Fin);
-    using Cfg = IowCfg<false, 1, LN>;
-    using Stack = IowStack<false>;
-    __shared__ float lds[kIowStack * Stack::kSlot * kBlock];
-    __shared__ short lds_bvh[Cfg::BS * kBlock];
-    __shared__ float4 s_nodes[LN ? kIowLdsNodes * 7 : 1];
-    short *bstk = lds_bvh + threadIdx.x;  // bslot's layout
-    const float4 *nodes = iow_stage_nodes<LN>(S, s_nodes);
-    Ctr c;
-    Stack K{lds + threadIdx.x, nullptr, 0};
-    const uint32_t lane = threadIdx.x & 63u;
-    // out_Pixel's per-frame scalars (03...glsl:370-380); the per-pixel ones are kept per lane
-    const int grid = iow_ring_grid(F.spp);
-    const float aspect = iow_aspect(F.W, F.H);
-    const float dsx = iow_px_dsx(aspect, F.W, grid), dsy = iow_px_dsy(F.H, grid);
-    uint32_t next = 0, end = 0;  // the wave's claimed range not handed out yet (wave-uniform)
-    bool drained = false;        // the queue is empty (wave-uniform)
-    bool busy = false;           // the lane owns a pixel: samples [s, s1) are left
-    bool walking = false;        // ... and sample s's path is under way
-    uint32_t s = 0, s1 = 0, out = 0;  // out = y * W + x < 2^31
-    int skip = 0;
-    float sx = 0.0f, sy = 0.0f;
-    f3 fc = f3{0, 0, 0}, ev = f3{0, 0, 0}, col = f3{0, 0, 0};
-    for (;;) {
-        while (!drained) {  // hand entries to the free lanes
-            const unsigned long long free = __ballot(!busy);
-            if (free == 0) break;
-            if (next >= end) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(queue, 64u * rounds);
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                if (base >= n_units) { drained = true; break; }
-                next = base;
-                end = n_units - base < 64u * rounds ? n_units : base + 64u * rounds;  // n_units <= 2^31
-            }
-            const uint32_t avail = end - next, want = (uint32_t)__popcll(free);
-            const uint32_t rank = lanes_below(free);
-            if (!busy && rank < avail) {
-                const int2 p = pixels[next + rank];
-                if (listed(F, p)) {  // an entry outside the image: the lane stays free
-                    out = (uint32_t)p.y * (uint32_t)F.W + (uint32_t)p.x;
-                    const float4 x = aux[out];
-                    s = __float_as_uint(x.w);
-                    ev = f3{x.x, x.y, x.z};
-                    fc = f3{0, 0, 0};
-                    if (s == 0) {
-                        ev = f3{0, 0, 0};
-                        for (int e = 0; e < kIowStack; e++) K.at(e, 7) = 0.0f;  // stale RI slots start at 0
-                    } else {
-                        const float4 a = state[2 * (size_t)out], r = state[2 * (size_t)out + 1];
-                        fc = f3{a.x, a.y, a.z};
-                        K.at(0, 7) = r.x; K.at(1, 7) = r.y; K.at(2, 7) = r.z; K.at(3, 7) = r.w;
-                    }
-                    if (s < stop) {
-                        s1 = ns < stop - s ? s + ns : stop;
-                        sx = iow_px_sx(aspect, p.x, F.W);
-                        sy = iow_px_sy(p.y, F.H);
-                        busy = true;
-                    } else {  // nothing left to render: the image from the state as it is
-                        if (F.out_rgba) {
-                            const f3 v = fc * rcp((float)s);
-                            reinterpret_cast<float4 *>(F.out_rgba)[out] = make_float4(v.x, v.y, v.z, 1.0f);
-                        }
-                        if (F.out_depth) F.out_depth[out] = 0.0f;
-                    }
-                }
-            }
-            next += want < avail ? want : avail;
-        }
-        if (busy && !walking) {  // start sample s
-            f3 ro, rd;
-            iow_camera_ray(S, F, sx, sy, dsx, dsy, (int)s, ro, rd);
-            K.size = 0;
-            K.wmask = K.rmask = 0u;
-            skip = 0;
-            col = f3{0, 0, 0};
-            K.push(ro, rd, 1.0f, 1.0f, 0, c);
-            walking = true;
-        }
-        if (__ballot(busy) == 0) {
-            if (drained) break;
-            continue;
-        }
-        if (walking) {
-            iow_segment<false, Cfg::BS, Cfg::NS>(S, Fs, K, skip, col, (int)s, c, bstk, nodes);
-            if (K.size == 0) {  // sample done: out_Pixel's sum, and the even samples' beside it
-                fc = fc + col;
-                if ((s & 1u) == 0) ev = ev + col;
-                s++;
-                walking = false;
-                if (s >= s1) {
-                    state[2 * (size_t)out] = make_float4(fc.x, fc.y, fc.z, 0.0f);
-                    state[2 * (size_t)out + 1] = make_float4(K.at(0, 7), K.at(1, 7), K.at(2, 7), K.at(3, 7));
-                    aux[out] = make_float4(ev.x, ev.y, ev.z, __uint_as_float(s));
-                    if (F.out_rgba) {
-                        const f3 v = fc * rcp((float)s);
-                        reinterpret_cast<float4 *>(F.out_rgba)[out] = make_float4(v.x, v.y, v.z, 1.0f);
-                    }
-                    if (F.out_depth) F.out_depth[out] = 0.0f;
-                    busy = false;
-                }
-            }
-        }
-    }
-    flush(F, c);
+    iow_pass_loop<LN>(Fin, S, ListPass{pixels, aux, stop, ns}, state, queue, rounds, n_units);
 }
 
 // ------------------------------------------------------------------------------------------ select
@@ -355,21 +223,12 @@ void k_select_scatter(Frame Fin, Select Q, uint32_t n_units, uint32_t n_blocks, 
 }
 
 // ------------------------------------------------------------------------------------------ launch
-constexpr uint32_t kAdaptRounds = 16;  // entries per claim: at most 16 x 64 (k_iow_pass's rule)
-
 namespace {
 int g_chunk_cap = 0;  // rt_debug_adaptive_chunk: 0 = none
 
 template <class Kn>
 hipError_t adapt_info(Kn kernel, int info[4]) {
-    hipFuncAttributes a;
-    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(kernel));
-    if (e != hipSuccess) return e;
-    info[0] = a.numRegs;
-    info[1] = (int)a.localSizeBytes;
-    info[2] = (int)a.sharedSizeBytes;
-    info[3] = occupancy_of(kernel, kBlock);
-    return hipSuccess;
+    return kernel_info(kernel, occupancy_of(kernel, kBlock), info);
 }
 // resident blocks per CU of the instance a scene runs, asked once each
 int iow_adapt_blocks(bool ln) {
@@ -419,16 +278,10 @@ hipError_t launch_iow_adapt(const Frame &f, const IowScene &sc, const int2 *pixe
     const hipError_t e = hipMemsetAsync(queue, 0, sizeof(unsigned), s);
     if (e != hipSuccess) return e;
     const bool ln = iow_lds(sc);
-    // the grid and the claim size: every wave of the grid gets at least four claims (k_iow_pass's rule)
-    const uint32_t need = (n_pixels + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
-    uint32_t cap = (uint32_t)(cus > 0 ? cus : 1) * (uint32_t)iow_adapt_blocks(ln);
-    const int max_blocks = pass_max_blocks_now();
-    if (max_blocks > 0 && (uint32_t)max_blocks < cap) cap = (uint32_t)max_blocks;
-    const dim3 g(need < cap ? need : cap), b(kBlock);
-    const uint32_t per_wave = n_pixels / (64u * g.x * (uint32_t)(kBlock / 64) * 4u);
-    const uint32_t rounds = per_wave < 1u ? 1u : (per_wave > kAdaptRounds ? kAdaptRounds : per_wave);
-    if (ln) hipLaunchKernelGGL((k_iow_adapt<true>), g, b, 0, s, f, sc, pixels, stop, ns, state, aux, queue, rounds, n_pixels);
-    else hipLaunchKernelGGL((k_iow_adapt<false>), g, b, 0, s, f, sc, pixels, stop, ns, state, aux, queue, rounds, n_pixels);
+    const ClaimGrid cg = claim_grid(n_pixels, cus, iow_adapt_blocks(ln), pass_max_blocks_now());
+    const dim3 g(cg.grid), b(kBlock);
+    if (ln) hipLaunchKernelGGL((k_iow_adapt<true>), g, b, 0, s, f, sc, pixels, stop, ns, state, aux, queue, cg.rounds, n_pixels);
+    else hipLaunchKernelGGL((k_iow_adapt<false>), g, b, 0, s, f, sc, pixels, stop, ns, state, aux, queue, cg.rounds, n_pixels);
     return hipGetLastError();
 }
 

@@ -164,6 +164,65 @@ int pixels_blocking(const rt_camera *cam, const rt_params *p, const rt_pixel *pi
     return st ? read_stats(d_ctr.p, ms, st) : RT_OK;
 }
 
+// The scene view of the INW queries and passes: as in the renders, only layout-1 walks read the sphere records,
+// and the fused cull needs the scene's culling boxes within 1000 of the origin (the kernels check each query's).
+rtk::InwScene inw_query_view(const rt_dev_scene *s) {
+    rtk::InwScene sc = inw_view(*s);
+    if (s->layout == 4) sc.sph = nullptr;
+    sc.fused = (s->opt.inw_fused_cull && sc.wnodes && s->walk.wbound <= 1000.0f) ? 1 : 0;
+    return sc;
+}
+
+// The samples a pass's shader runs: IOW-03 stops at the ring schedule's early return (k_iow03's s_stop).
+uint32_t pass_stop(const rt_dev_scene *s) { return uint32_t(s->kind == 3 ? s->s_stop : s->spp); }
+
+// A pass's frame: make_frame's with the caller's outputs and counters.
+rtk::Frame make_pass_frame(const rt_dev_scene *s, const rt_camera *cam, const rt_params *p, float *d_rgba,
+                           float *d_depth, uint64_t *d_counters) {
+    rtk::Frame f = make_frame(cam, p);
+    f.out_rgba = d_rgba; f.out_depth = d_depth;
+    f.counters = reinterpret_cast<unsigned long long *>(d_counters);
+    f.dbg = nullptr; f.px_rays = nullptr;  // the renders' diagnostics hooks do not apply
+    f.leaf_batch = s->opt.iow_leaf_batch;
+    return f;
+}
+
+// rt_debug_pass_max_blocks caps the paths' grid while one of these lives; the paths' own cap is back after it.
+struct PassBlockCap {
+    const int prev = rtk::inw_paths_max_blocks(rtk::pass_max_blocks_now());
+    ~PassBlockCap() { (void)rtk::inw_paths_max_blocks(prev); }
+};
+
+// The INW half of a pass, `total` samples of each of n pixels (units or list entries): per chunk [c0, c0 + nsc)
+// of them, the camera rays into the scene's pass workspace (rays_of), the path queries on them
+// (rt_path_rays_async's launch: its scene view, its queue word, its fused-cull rule) and the fold (fold_of).
+// A chunk is as many samples as keep the rays and answers (64 B a sample and pixel) within kPassRecords records,
+// chunk_cap > 0 at most; the first pass of a frame size and chunk grows the workspace, later ones allocate none.
+template <class Rays, class Fold>
+int pass_inw_chunks(rt_dev_scene *s, const rt_camera *cam, const rt_params *p, uint32_t n, uint32_t total,
+                    int chunk_cap, uint64_t *d_counters, hipStream_t st, Rays &&rays_of, Fold &&fold_of) {
+    constexpr uint64_t kPassRecords = uint64_t(1) << 25;
+    uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(total, kPassRecords / n)));
+    if (chunk_cap > 0) chunk = std::min(chunk, uint32_t(chunk_cap));
+    HIP_OK(s->pass_ws.reserve(size_t(n) * chunk * 2 * sizeof(rt_path_ray)));
+    float4 *rays = s->pass_ws.as<float4>(), *out = rays + size_t(n) * chunk * 2;
+    const rtk::InwScene sc = inw_query_view(s);
+    // the frame's child order: dot(dir, (1, 1, 1)) > 0 in binary32, the shader's order (inw_segment)
+    const float dsum = (cam->dir[0] * 1.0f + cam->dir[1] * 1.0f) + cam->dir[2] * 1.0f;
+    unsigned *queue = s->counter.as<unsigned>() + 224;
+    const PassBlockCap cap;
+    hipError_t e = hipSuccess;
+    for (uint32_t c0 = 0; c0 < total && e == hipSuccess; c0 += chunk) {
+        const uint32_t nsc = std::min(chunk, total - c0);
+        e = rays_of(sc, c0, nsc, rays);
+        if (e == hipSuccess)
+            e = rtk::launch_inw_paths(sc, rays, n * nsc, s->spp, p->max_bounces, dsum > 0.0f, out,
+                                      reinterpret_cast<unsigned long long *>(d_counters), queue, s->cus, st);
+        if (e == hipSuccess) e = fold_of(c0, nsc, c0 + nsc == total, out);
+    }
+    return e == hipSuccess ? RT_OK : launch_failed(e);
+}
+
 // Progressive passes: cuts is strictly increasing from cuts[0] > 0 to at most spp.
 bool cuts_ok(const rt_params *p, const uint32_t *cuts, int n_cuts) {
     if (!cuts || n_cuts < 1 || cuts[0] == 0 || cuts[n_cuts - 1] > uint32_t(p->spp)) return false;
@@ -678,12 +737,7 @@ int rt_trace_rays_async(rt_dev_scene *s, const rt_ray *d_rays, uint32_t n_rays, 
     if (s->broken || n_rays > (1u << 31)) return RT_E_ARG;
     if (n_rays == 0) return RT_OK;
     if (!d_rays || !d_hits) return RT_E_ARG;
-    rtk::InwScene sc = inw_view(*s);
-    // as in the renders, only layout-1 walks read the sphere records (INW-04's kernels compile them out)
-    if (s->layout == 4) sc.sph = nullptr;
-    // the fused cull under the render path's rule (launch_scene_inw_fold): the scene's culling
-    // boxes within 1000 of the origin; the kernel checks each query's origin
-    sc.fused = (s->opt.inw_fused_cull && sc.wnodes && s->walk.wbound <= 1000.0f) ? 1 : 0;
+    const rtk::InwScene sc = inw_query_view(s);
     // its own queue counter, past the fold kernels' (two queues 64 B apart and 8 XCD queues from byte 256)
     unsigned *queue = s->counter.as<unsigned>() + 240;
     const hipError_t e = rtk::launch_inw_trace(sc, reinterpret_cast<const float4 *>(d_rays), n_rays,
@@ -743,12 +797,7 @@ int rt_path_rays_async(rt_dev_scene *s, const rt_path_ray *d_rays, uint32_t n_ra
     if (s->broken || n_rays > (1u << 31)) return RT_E_ARG;
     if (n_rays == 0) return RT_OK;
     if (!d_rays || !d_out) return RT_E_ARG;
-    rtk::InwScene sc = inw_view(*s);
-    // as in the renders and rt_trace_rays_async: only layout-1 walks read the sphere records, and the
-    // fused cull needs the scene's culling boxes within 1000 of the origin (the kernel checks each
-    // query's origin)
-    if (s->layout == 4) sc.sph = nullptr;
-    sc.fused = (s->opt.inw_fused_cull && sc.wnodes && s->walk.wbound <= 1000.0f) ? 1 : 0;
+    const rtk::InwScene sc = inw_query_view(s);
     // its own queue counter: clear of the fold kernels' (bytes 0..767) and the ray queries' (word 240)
     unsigned *queue = s->counter.as<unsigned>() + 224;
     const hipError_t e = rtk::launch_inw_paths(sc, reinterpret_cast<const float4 *>(d_rays), n_rays, s->spp,
@@ -899,51 +948,25 @@ int rt_render_pass_async(rt_dev_scene *s, const rt_camera *cam, const rt_params 
         return RT_E_ARG;
     if (p->show_normal) return RT_E_UNSUPPORTED;  // one normal per sample, no fold state
     if (ns == 0) return RT_OK;
-    const bool iow = s->kind == 3;
-    // the samples the shader runs: IOW-03 stops at the ring schedule's early return (k_iow03's s_stop)
-    const uint32_t stop = uint32_t(iow ? s->s_stop : s->spp);
-    const uint32_t s1 = uint32_t(std::min<uint64_t>(uint64_t(s0) + ns, stop));
-    rtk::Frame f = make_frame(cam, p);
-    f.out_rgba = d_rgba; f.out_depth = d_depth;
-    f.counters = reinterpret_cast<unsigned long long *>(d_counters);
-    f.dbg = nullptr; f.px_rays = nullptr;  // the renders' diagnostics hooks do not apply
-    f.leaf_batch = s->opt.iow_leaf_batch;
+    const uint32_t s1 = uint32_t(std::min<uint64_t>(uint64_t(s0) + ns, pass_stop(s)));
+    const rtk::Frame f = make_pass_frame(s, cam, p, d_rgba, d_depth, d_counters);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     float4 *state = reinterpret_cast<float4 *>(d_state);
-    if (iow) {
+    if (s->kind == 3) {
         // its own queue counter: clear of the fold kernels' (bytes 0..767) and the queries' (words 208, 224, 240)
         unsigned *queue = s->counter.as<unsigned>() + 192;
         const hipError_t e = rtk::launch_iow_pass(f, iow_view(*s), s0, s1, state, queue, s->cus, st);
         return e == hipSuccess ? RT_OK : launch_failed(e);
     }
-    // INW: per chunk of samples, the camera rays into the scene's pass workspace, the path queries on them
-    // (rt_path_rays_async's launch: its scene view, its queue word, its fused-cull rule) and the fold.
-    // A chunk is as many samples as keep the rays and answers (64 B a sample and unit) within kPassRecords
-    // records; the first pass of a frame size and chunk grows the workspace, later ones allocate nothing.
-    constexpr uint64_t kPassRecords = uint64_t(1) << 25;
     const uint32_t units = rtk::units_of(f);
     if (units == 0 || units > (1u << 31)) return RT_E_ARG;
-    const uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(s1 - s0, kPassRecords / units)));
-    HIP_OK(s->pass_ws.reserve(size_t(units) * chunk * 2 * sizeof(rt_path_ray)));
-    float4 *rays = s->pass_ws.as<float4>(), *out = rays + size_t(units) * chunk * 2;
-    rtk::InwScene sc = inw_view(*s);
-    if (s->layout == 4) sc.sph = nullptr;
-    sc.fused = (s->opt.inw_fused_cull && sc.wnodes && s->walk.wbound <= 1000.0f) ? 1 : 0;
-    // the frame's child order: dot(dir, (1, 1, 1)) > 0 in binary32, the shader's order (inw_segment)
-    const float dsum = (cam->dir[0] * 1.0f + cam->dir[1] * 1.0f) + cam->dir[2] * 1.0f;
-    unsigned *queue = s->counter.as<unsigned>() + 224;
-    const int cap = rtk::inw_paths_max_blocks(rtk::pass_max_blocks_now());  // rt_debug_pass_max_blocks caps the paths' grid
-    hipError_t e = hipSuccess;
-    for (uint32_t c0 = s0; c0 < s1 && e == hipSuccess; c0 += chunk) {
-        const uint32_t nsc = std::min(chunk, s1 - c0);
-        e = rtk::launch_pass_rays(f, sc, c0, nsc, rays, st);
-        if (e == hipSuccess)
-            e = rtk::launch_inw_paths(sc, rays, units * nsc, s->spp, p->max_bounces, dsum > 0.0f, out,
-                                      reinterpret_cast<unsigned long long *>(d_counters), queue, s->cus, st);
-        if (e == hipSuccess) e = rtk::launch_pass_fold(f, c0, nsc, c0 + nsc == s1 ? s1 : 0u, out, state, st);
-    }
-    (void)rtk::inw_paths_max_blocks(cap);
-    return e == hipSuccess ? RT_OK : launch_failed(e);
+    return pass_inw_chunks(s, cam, p, units, s1 - s0, 0, d_counters, st,
+        [&](const rtk::InwScene &sc, uint32_t c0, uint32_t nsc, float4 *rays) {
+            return rtk::launch_pass_rays(f, sc, s0 + c0, nsc, rays, st);
+        },
+        [&](uint32_t c0, uint32_t nsc, bool last, const float4 *out) {
+            return rtk::launch_pass_fold(f, s0 + c0, nsc, last ? s1 : 0u, out, state, st);
+        });
 }
 
 int rt_render_passes_inw(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
@@ -978,50 +1001,27 @@ int rt_render_pass_pixels_async(rt_dev_scene *s, const rt_camera *cam, const rt_
     if (n_pixels > (1u << 31) || (n_pixels > 0 && !d_pixels)) return RT_E_ARG;
     if (p->show_normal) return RT_E_UNSUPPORTED;  // one normal per sample, no fold state
     if (n_pixels == 0 || ns == 0) return RT_OK;
-    const bool iow = s->kind == 3;
-    const uint32_t stop = uint32_t(iow ? s->s_stop : s->spp);  // rt_render_pass_async's S
-    ns = std::min(ns, stop);                                    // no pixel has more samples left
+    const uint32_t stop = pass_stop(s);
+    ns = std::min(ns, stop);  // no pixel has more samples left
     rt_params whole = *p;
     whole.tile_w = whole.tile_h = 0;  // the list says which pixels
-    rtk::Frame f = make_frame(cam, &whole);
-    f.out_rgba = d_rgba; f.out_depth = d_depth;
-    f.counters = reinterpret_cast<unsigned long long *>(d_counters);
-    f.dbg = nullptr; f.px_rays = nullptr;  // the renders' diagnostics hooks do not apply
-    f.leaf_batch = s->opt.iow_leaf_batch;
+    const rtk::Frame f = make_pass_frame(s, cam, &whole, d_rgba, d_depth, d_counters);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     float4 *state = reinterpret_cast<float4 *>(d_state), *aux = reinterpret_cast<float4 *>(d_aux);
     const int2 *px = reinterpret_cast<const int2 *>(d_pixels);
-    if (iow) {
+    if (s->kind == 3) {
         unsigned *queue = s->counter.as<unsigned>() + 192;  // the passes' own: calls on one scene do not overlap
         const hipError_t e = rtk::launch_iow_adapt(f, iow_view(*s), px, n_pixels, stop, ns, state, aux, queue, s->cus, st);
         return e == hipSuccess ? RT_OK : launch_failed(e);
     }
-    // INW: rt_render_pass_async's chunks, driven by the list: n_pixels * chunk records of rays and answers in
-    // the scene's pass workspace; every chunk's fold advances the counts the next chunk's rays start from.
-    constexpr uint64_t kPassRecords = uint64_t(1) << 25;
-    uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(ns, kPassRecords / n_pixels)));
-    const int cap_chunk = rtk::adaptive_chunk_cap_now();  // rt_debug_adaptive_chunk
-    if (cap_chunk > 0) chunk = std::min(chunk, uint32_t(cap_chunk));
-    HIP_OK(s->pass_ws.reserve(size_t(n_pixels) * chunk * 2 * sizeof(rt_path_ray)));
-    float4 *rays = s->pass_ws.as<float4>(), *out = rays + size_t(n_pixels) * chunk * 2;
-    rtk::InwScene sc = inw_view(*s);
-    if (s->layout == 4) sc.sph = nullptr;
-    sc.fused = (s->opt.inw_fused_cull && sc.wnodes && s->walk.wbound <= 1000.0f) ? 1 : 0;
-    // the frame's child order: dot(dir, (1, 1, 1)) > 0 in binary32, the shader's order (inw_segment)
-    const float dsum = (cam->dir[0] * 1.0f + cam->dir[1] * 1.0f) + cam->dir[2] * 1.0f;
-    unsigned *queue = s->counter.as<unsigned>() + 224;
-    const int cap = rtk::inw_paths_max_blocks(rtk::pass_max_blocks_now());  // rt_debug_pass_max_blocks caps the paths' grid
-    hipError_t e = hipSuccess;
-    for (uint32_t c0 = 0; c0 < ns && e == hipSuccess; c0 += chunk) {
-        const uint32_t nsc = std::min(chunk, ns - c0);
-        e = rtk::launch_adapt_rays(f, sc, px, n_pixels, aux, stop, nsc, rays, st);
-        if (e == hipSuccess)
-            e = rtk::launch_inw_paths(sc, rays, n_pixels * nsc, s->spp, p->max_bounces, dsum > 0.0f, out,
-                                      reinterpret_cast<unsigned long long *>(d_counters), queue, s->cus, st);
-        if (e == hipSuccess) e = rtk::launch_adapt_fold(f, px, n_pixels, stop, nsc, c0 + nsc == ns, out, state, aux, st);
-    }
-    (void)rtk::inw_paths_max_blocks(cap);
-    return e == hipSuccess ? RT_OK : launch_failed(e);
+    // every chunk's fold advances the counts the next chunk's rays start from; rt_debug_adaptive_chunk caps it
+    return pass_inw_chunks(s, cam, p, n_pixels, ns, rtk::adaptive_chunk_cap_now(), d_counters, st,
+        [&](const rtk::InwScene &sc, uint32_t, uint32_t nsc, float4 *rays) {
+            return rtk::launch_adapt_rays(f, sc, px, n_pixels, aux, stop, nsc, rays, st);
+        },
+        [&](uint32_t, uint32_t nsc, bool last, const float4 *out) {
+            return rtk::launch_adapt_fold(f, px, n_pixels, stop, nsc, last, out, state, aux, st);
+        });
 }
 
 int rt_pass_select_async(rt_dev_scene *s, const rt_params *p, const rt_pass_state *d_state, const rt_pass_aux *d_aux,
@@ -1033,9 +1033,8 @@ int rt_pass_select_async(rt_dev_scene *s, const rt_params *p, const rt_pass_stat
     const uint32_t units = rtk::units_of(f);
     if (units == 0 || units > (1u << 31)) return RT_E_ARG;
     HIP_OK(s->select_ws.reserve((size_t(rtk::select_blocks(f)) + 1) * sizeof(uint2)));
-    const uint32_t stop = uint32_t(s->kind == 3 ? s->s_stop : s->spp);
     const hipError_t e = rtk::launch_pass_select(f, reinterpret_cast<const float4 *>(d_state),
-                                                 reinterpret_cast<const float4 *>(d_aux), tol, min_samples, stop,
+                                                 reinterpret_cast<const float4 *>(d_aux), tol, min_samples, pass_stop(s),
                                                  reinterpret_cast<int2 *>(d_list), d_n_active, d_err,
                                                  s->select_ws.as<uint2>(), static_cast<hipStream_t>(stream));
     return e == hipSuccess ? RT_OK : launch_failed(e);

@@ -522,6 +522,43 @@ hipError_t launch_pass_select(const Frame &f, const float4 *state, const float4 
 hipError_t adaptive_kernel_info(int which, int info[4]);
 int adaptive_chunk_cap_now();          // the cap rt_debug_adaptive_chunk set (0 = none)
 int adaptive_chunk_cap(int samples);   // rt_debug_adaptive_chunk: cap an INW chunk's samples (0 = off); the previous cap
+// What the units that own kernels share on the launch side.
+// Resident blocks per CU of `kernel` at `block` lanes (2 if the query fails): each unit answers
+// resident_blocks_per_cu and its *_blocks_per_cu for the kernels it owns.
+template <class K>
+int occupancy_of(K kernel, int block) {
+    int nb = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, 0);
+    return (e == hipSuccess && nb > 0) ? nb : 2;
+}
+// A kernel's {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} (hipFuncGetAttributes and the
+// unit's own occupancy answer): what every *_kernel_info returns.
+template <class K>
+hipError_t kernel_info(K kernel, int blocks_per_cu, int info[4]) {
+    hipFuncAttributes a;
+    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(kernel));
+    if (e != hipSuccess) return e;
+    info[0] = a.numRegs;
+    info[1] = (int)a.localSizeBytes;
+    info[2] = (int)a.sharedSizeBytes;
+    info[3] = blocks_per_cu;
+    return hipSuccess;
+}
+// The launch rule of a persistent grid of kBlock-lane blocks over n work items, whose waves claim
+// 64 * rounds consecutive items with one atomic: at most cus * blocks_per_cu blocks (the resident grid;
+// max_blocks > 0: a debug cap below it), and as many 64s per claim, kClaimRounds at most, as leave every
+// wave of the grid at least four claims (the tail of a batch stays balanced; a small batch claims 64 at a
+// time).
+constexpr uint32_t kClaimRounds = 16;  // measured on C2 (k_iow_trace): 1 -> 5.5, 4 -> 20.9, 16 -> 32.6 G primary queries/s
+struct ClaimGrid { uint32_t grid, rounds; };
+inline ClaimGrid claim_grid(uint32_t n, int cus, int blocks_per_cu, int max_blocks) {
+    const uint32_t need = (n + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
+    uint32_t cap = (uint32_t)(cus > 0 ? cus : 1) * (uint32_t)blocks_per_cu;
+    if (max_blocks > 0 && (uint32_t)max_blocks < cap) cap = (uint32_t)max_blocks;
+    const uint32_t grid = need < cap ? need : cap;
+    const uint32_t per_wave = grid ? n / (64u * grid * (uint32_t)(kBlock / 64) * 4u) : 0u;  // (n = 0: no grid)
+    return ClaimGrid{grid, per_wave < 1u ? 1u : (per_wave > kClaimRounds ? kClaimRounds : per_wave)};
+}
 // The persistent render kernels, by name, and the resident blocks per CU of each (occupancy query;
 // 2 if it fails).  The kernels are private to their units, so resident_blocks_per_cu
 // (rt_iow_render.hip) asks the unit that owns the kernel.

@@ -1,7 +1,10 @@
 // rt_pass_common.hpp -- what the pass units share (rt_passes.hip, rt_adaptive.hip): the camera-ray catcher of
-// inw_start_sample and the frame as the pass kernels rebuild it.
+// inw_start_sample, the frame as the pass kernels rebuild it, a list entry's test, the image write, and for
+// the INW pairs (k_pass_rays / k_adapt_rays, k_pass_fold / k_adapt_fold) the record writer and the fold's
+// start from the state.  The IOW-03 loop is in rt_pass_loop.hpp.
 #pragma once
 #include "rt_render_common.hpp"
+#include "rt_inw_shade.hpp"
 
 namespace rtk {
 
@@ -30,6 +33,48 @@ __device__ __forceinline__ void pass_seg_frame(Frame &F, const Frame &in) {
     F.inv_spp = in.inv_spp;
     F.dir[0] = in.dir[0]; F.dir[1] = in.dir[1]; F.dir[2] = in.dir[2];
     F.leaf_batch = in.leaf_batch;
+}
+
+// A list entry: inside the image or skipped ({-1, -1} is rt_pass_select_async's padding).
+__device__ __forceinline__ bool listed(const Frame &F, int2 p) {
+    return p.x >= 0 && p.y >= 0 && p.x < F.W && p.y < F.H;
+}
+
+// The image of a pixel with k samples folded: acc * RN(1 / k), and the depth.
+__device__ __forceinline__ void pass_write_image(const Frame &F, size_t o, f3 acc, float inv_k, float depth) {
+    if (F.out_rgba) {
+        const f3 v = acc * inv_k;
+        reinterpret_cast<float4 *>(F.out_rgba)[o] = make_float4(v.x, v.y, v.z, 1.0f);
+    }
+    if (F.out_depth) F.out_depth[o] = depth;
+}
+
+// ------------------------------------------------------------------------------------------ INW
+// A path-query record (rt_path_ray: origin, sample | direction, pad): the camera ray of sample s of pixel
+// (x, y) by the render's own sample start ...
+__device__ __forceinline__ void pass_ray_record(const InwScene &S, const Frame &F, int x, int y, uint32_t s, float4 *r) {
+    PassRay K;
+    Ctr c;
+    inw_start_sample(S, F, K, x, y, (int)s, c);
+    r[0] = make_float4(K.o.x, K.o.y, K.o.z, __uint_as_float(s));
+    r[1] = make_float4(K.d.x, K.d.y, K.d.z, 0.0f);
+}
+// ... or the record of no sample (0xffffffff), which the path kernel answers without a path.
+__device__ __forceinline__ void pass_no_record(float4 *r) {
+    r[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xffffffffu));
+    r[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// Where End()'s fold of the pixel at o starts from sample c: its state (rt_pass_state's first float4: the
+// sum, the depth of sample spp / 2), not read when c == 0, where the first sample is assigned.
+__device__ __forceinline__ void pass_fold_begin(const float4 *state, size_t o, uint32_t c, f3 &acc, float &dmid) {
+    acc = f3{0, 0, 0};
+    dmid = 0.0f;
+    if (c != 0) {
+        const float4 a = state[2 * o];
+        acc = f3{a.x, a.y, a.z};
+        dmid = a.w;
+    }
 }
 
 }  // namespace rtk

@@ -132,30 +132,17 @@ void k_iow_paths(IowScene S, int leaf_batch, int max_bounces, const float4 *__re
     }
 }
 
-constexpr uint32_t kPathIowRounds = 16;  // chains per claim: at most 16 x 64 (the rule of launch_inw_paths)
-
 namespace {
 int g_max_blocks = 0;  // rt_debug_path_iow_max_blocks: 0 = the resident grid
 
 template <bool LN>
 int path_iow_blocks() {  // resident blocks per CU, asked once
-    static const int nb = [] {
-        int n = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_iow_paths<LN>, kBlock, 0);
-        return (e == hipSuccess && n > 0) ? n : 2;
-    }();
+    static const int nb = occupancy_of(k_iow_paths<LN>, kBlock);
     return nb;
 }
 template <bool LN>
 hipError_t path_iow_info(int info[4]) {
-    hipFuncAttributes a;
-    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_iow_paths<LN>));
-    if (e != hipSuccess) return e;
-    info[0] = a.numRegs;
-    info[1] = (int)a.localSizeBytes;
-    info[2] = (int)a.sharedSizeBytes;
-    info[3] = path_iow_blocks<LN>();
-    return hipSuccess;
+    return kernel_info(k_iow_paths<LN>, path_iow_blocks<LN>(), info);
 }
 }  // namespace
 
@@ -178,16 +165,10 @@ hipError_t launch_iow_paths(const IowScene &sc, int leaf_batch, int max_bounces,
     if (e != hipSuccess) return e;
     const bool ln = iow_lds(sc);
     const uint32_t n_chains = n_rays / chain + (n_rays % chain ? 1u : 0u);  // the last chain may be short
-    const uint32_t need = (n_chains + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
-    uint32_t cap = (uint32_t)(cus > 0 ? cus : 1) * (uint32_t)iow_paths_blocks_per_cu(ln);
-    if (g_max_blocks > 0 && (uint32_t)g_max_blocks < cap) cap = (uint32_t)g_max_blocks;
-    const dim3 g(need < cap ? need : cap), b(kBlock);
-    // chains per claim: as many 64s as leave every wave of the grid at least four claims (the tail
-    // of a batch stays balanced; a small batch claims 64 at a time)
-    const uint32_t per_wave = n_chains / (64u * g.x * (uint32_t)(kBlock / 64) * 4u);
-    const uint32_t rounds = per_wave < 1u ? 1u : (per_wave > kPathIowRounds ? kPathIowRounds : per_wave);
-    if (ln) hipLaunchKernelGGL((k_iow_paths<true>), g, b, 0, s, sc, leaf_batch, max_bounces, rays, n_rays, chain, n_chains, (uint32_t)spp, out, counters, queue, rounds);
-    else hipLaunchKernelGGL((k_iow_paths<false>), g, b, 0, s, sc, leaf_batch, max_bounces, rays, n_rays, chain, n_chains, (uint32_t)spp, out, counters, queue, rounds);
+    const ClaimGrid cg = claim_grid(n_chains, cus, iow_paths_blocks_per_cu(ln), g_max_blocks);
+    const dim3 g(cg.grid), b(kBlock);
+    if (ln) hipLaunchKernelGGL((k_iow_paths<true>), g, b, 0, s, sc, leaf_batch, max_bounces, rays, n_rays, chain, n_chains, (uint32_t)spp, out, counters, queue, cg.rounds);
+    else hipLaunchKernelGGL((k_iow_paths<false>), g, b, 0, s, sc, leaf_batch, max_bounces, rays, n_rays, chain, n_chains, (uint32_t)spp, out, counters, queue, cg.rounds);
     return hipGetLastError();
 }
 

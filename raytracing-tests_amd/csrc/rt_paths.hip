@@ -110,30 +110,17 @@ void k_inw_paths(InwScene S, const float4 *__restrict__ rays, uint32_t n_rays, u
     }
 }
 
-constexpr uint32_t kPathRounds = 16;  // queries per claim: at most 16 x 64 (the rule of launch_iow_trace)
-
 namespace {
 int g_max_blocks = 0;  // rt_debug_paths_max_blocks: 0 = the resident grid
 
 template <bool LIGHTS, bool FU>
 int paths_blocks() {  // resident blocks per CU, asked once
-    static const int nb = [] {
-        int n = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_inw_paths<LIGHTS, FU>, kBlock, 0);
-        return (e == hipSuccess && n > 0) ? n : 2;
-    }();
+    static const int nb = occupancy_of(k_inw_paths<LIGHTS, FU>, kBlock);
     return nb;
 }
 template <bool LIGHTS, bool FU>
 hipError_t paths_info(int info[4]) {
-    hipFuncAttributes a;
-    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_inw_paths<LIGHTS, FU>));
-    if (e != hipSuccess) return e;
-    info[0] = a.numRegs;
-    info[1] = (int)a.localSizeBytes;
-    info[2] = (int)a.sharedSizeBytes;
-    info[3] = paths_blocks<LIGHTS, FU>();
-    return hipSuccess;
+    return kernel_info(k_inw_paths<LIGHTS, FU>, paths_blocks<LIGHTS, FU>(), info);
 }
 }  // namespace
 
@@ -159,22 +146,16 @@ hipError_t launch_inw_paths(const InwScene &sc, const float4 *rays, uint32_t n_r
     const hipError_t e = hipMemsetAsync(queue, 0, sizeof(unsigned), s);
     if (e != hipSuccess) return e;
     const bool lights = sc.layout == 4, fu = sc.fused != 0;
-    const uint32_t need = (n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
-    uint32_t cap = (uint32_t)(cus > 0 ? cus : 1) * (uint32_t)inw_paths_blocks_per_cu(lights, fu);
-    if (g_max_blocks > 0 && (uint32_t)g_max_blocks < cap) cap = (uint32_t)g_max_blocks;
-    const dim3 g(need < cap ? need : cap), b(kBlock);
-    // queries per claim: as many 64s as leave every wave of the grid at least four claims (the tail
-    // of a batch stays balanced; a small batch claims 64 at a time)
-    const uint32_t per_wave = n_rays / (64u * g.x * (uint32_t)(kBlock / 64) * 4u);
-    const uint32_t rounds = per_wave < 1u ? 1u : (per_wave > kPathRounds ? kPathRounds : per_wave);
+    const ClaimGrid cg = claim_grid(n_rays, cus, inw_paths_blocks_per_cu(lights, fu), g_max_blocks);
+    const dim3 g(cg.grid), b(kBlock);
     const float inv_spp = 1.0f / (float)spp;  // as make_frame forms it
     const uint32_t inv = invert ? 1u : 0u;
     if (lights) {
-        if (fu) hipLaunchKernelGGL((k_inw_paths<true, true>), g, b, 0, s, sc, rays, n_rays, (uint32_t)spp, max_bounces, inv_spp, inv, out, counters, queue, rounds);
-        else hipLaunchKernelGGL((k_inw_paths<true, false>), g, b, 0, s, sc, rays, n_rays, (uint32_t)spp, max_bounces, inv_spp, inv, out, counters, queue, rounds);
+        if (fu) hipLaunchKernelGGL((k_inw_paths<true, true>), g, b, 0, s, sc, rays, n_rays, (uint32_t)spp, max_bounces, inv_spp, inv, out, counters, queue, cg.rounds);
+        else hipLaunchKernelGGL((k_inw_paths<true, false>), g, b, 0, s, sc, rays, n_rays, (uint32_t)spp, max_bounces, inv_spp, inv, out, counters, queue, cg.rounds);
     } else {
-        if (fu) hipLaunchKernelGGL((k_inw_paths<false, true>), g, b, 0, s, sc, rays, n_rays, (uint32_t)spp, max_bounces, inv_spp, inv, out, counters, queue, rounds);
-        else hipLaunchKernelGGL((k_inw_paths<false, false>), g, b, 0, s, sc, rays, n_rays, (uint32_t)spp, max_bounces, inv_spp, inv, out, counters, queue, rounds);
+        if (fu) hipLaunchKernelGGL((k_inw_paths<false, true>), g, b, 0, s, sc, rays, n_rays, (uint32_t)spp, max_bounces, inv_spp, inv, out, counters, queue, cg.rounds);
+        else hipLaunchKernelGGL((k_inw_paths<false, false>), g, b, 0, s, sc, rays, n_rays, (uint32_t)spp, max_bounces, inv_spp, inv, out, counters, queue, cg.rounds);
     }
     return hipGetLastError();
 }

@@ -142,29 +142,12 @@ void k_pixel_fold(Frame F, const int2 *__restrict__ pixels, uint32_t n_pixels, c
                                          __uint_as_float((uint32_t)nans));
 }
 
-namespace {
-template <class K>
-hipError_t kernel_info(K kernel, int block, int info[4]) {
-    hipFuncAttributes a;
-    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(kernel));
-    if (e != hipSuccess) return e;
-    int nb = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, 0);
-    if (e != hipSuccess) return e;
-    info[0] = a.numRegs;
-    info[1] = (int)a.localSizeBytes;
-    info[2] = (int)a.sharedSizeBytes;
-    info[3] = nb;
-    return hipSuccess;
-}
-}  // namespace
-
 hipError_t pixels_kernel_info(int which, int info[4]) {
     switch (which) {
-        case 0: return kernel_info(k_camera_rays<false>, kBlock, info);
-        case 1: return kernel_info(k_camera_rays<true>, kBlock, info);
-        case 2: return kernel_info(k_pixel_fold<false>, kBlock, info);
-        case 3: return kernel_info(k_pixel_fold<true>, kBlock, info);
+        case 0: return kernel_info(k_camera_rays<false>, occupancy_of(k_camera_rays<false>, kBlock), info);
+        case 1: return kernel_info(k_camera_rays<true>, occupancy_of(k_camera_rays<true>, kBlock), info);
+        case 2: return kernel_info(k_pixel_fold<false>, occupancy_of(k_pixel_fold<false>, kBlock), info);
+        case 3: return kernel_info(k_pixel_fold<true>, occupancy_of(k_pixel_fold<true>, kBlock), info);
     }
     return hipErrorInvalidValue;
 }

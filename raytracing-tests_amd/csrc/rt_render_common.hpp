@@ -1,6 +1,7 @@
 // rt_render_common.hpp -- what the render units share (rt_iow_render.hip, rt_iow_spec.hip,
 // rt_inw_render.hip, rt_inw_fold.hip): the pixel mappings, the persistent work queue's
-// wave-aggregated claims, the counter flush, and the launch side's grid size and occupancy query.
+// wave-aggregated claims, the counter flush, and the launch side's grid size (the occupancy query is
+// rt_kernels.hpp's occupancy_of).
 //
 // One thread renders one pixel and walks its samples in order, exactly like the
 // reference's invocation (IOW) or workgroup (INW) does, so the per-pixel reduction order
@@ -149,14 +150,6 @@ static unsigned grid_of(uint32_t units, int blocks_cap) {
     uint64_t b = ((uint64_t)units + kBlock - 1) / kBlock;
     if (b > (uint64_t)blocks_cap) b = blocks_cap;
     return (unsigned)(b ? b : 1);
-}
-// resident blocks per CU of `kernel` at `block` lanes (2 if the query fails): each unit answers
-// resident_blocks_per_cu for the kernels it owns
-template <class K>
-static int occupancy_of(K kernel, int block) {
-    int nb = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, 0);
-    return (e == hipSuccess && nb > 0) ? nb : 2;
 }
 
 }  // namespace rtk

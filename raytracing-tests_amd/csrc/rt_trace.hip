@@ -66,23 +66,12 @@ __global__ __launch_bounds__(kBlock) void k_inw_trace(InwScene S, const float4 *
 namespace {
 template <bool ANY, bool FU>
 int trace_blocks() {  // resident blocks per CU, asked once
-    static const int nb = [] {
-        int n = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_inw_trace<ANY, FU>, kBlock, 0);
-        return (e == hipSuccess && n > 0) ? n : 2;
-    }();
+    static const int nb = occupancy_of(k_inw_trace<ANY, FU>, kBlock);
     return nb;
 }
 template <bool ANY, bool FU>
 hipError_t trace_info(int info[4]) {
-    hipFuncAttributes a;
-    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_inw_trace<ANY, FU>));
-    if (e != hipSuccess) return e;
-    info[0] = a.numRegs;
-    info[1] = (int)a.localSizeBytes;
-    info[2] = (int)a.sharedSizeBytes;
-    info[3] = trace_blocks<ANY, FU>();
-    return hipSuccess;
+    return kernel_info(k_inw_trace<ANY, FU>, trace_blocks<ANY, FU>(), info);
 }
 }  // namespace
 
@@ -101,9 +90,7 @@ hipError_t launch_inw_trace(const InwScene &sc, const float4 *rays, uint32_t n_r
     const hipError_t e = hipMemsetAsync(queue, 0, sizeof(unsigned), s);
     if (e != hipSuccess) return e;
     const bool fu = sc.fused != 0;
-    const uint32_t need = (n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
-    const uint32_t cap = (uint32_t)(cus > 0 ? cus : 1) * (uint32_t)inw_trace_blocks_per_cu(any, fu);
-    const dim3 g(need < cap ? need : cap), b(kBlock);
+    const dim3 g(claim_grid(n_rays, cus, inw_trace_blocks_per_cu(any, fu), 0).grid), b(kBlock);  // claims of 64
     const uint32_t inv = invert ? 1u : 0u;
     if (any) {
         if (fu) hipLaunchKernelGGL((k_inw_trace<true, true>), g, b, 0, s, sc, rays, n_rays, inv, hits, counters, queue);

@@ -14,7 +14,7 @@ namespace rtk {
 // 64 * rounds consecutive queries from `queue` with one atomic and answers them 64 at a time, until
 // none are left.  One claim per 64 queries caps the kernel at about 5.5 G queries/s on an MI355X
 // whatever the rays (the same-address atomics serialise, about 12 ns each: DESIGN.md 5.8), so large
-// batches claim up to kIowTraceRounds x 64 (launch_iow_trace).
+// batches claim up to kClaimRounds x 64 (claim_grid).
 // LN: the scene's 4-wide BVH (at most kIowLdsNodes nodes) is staged in the block's LDS at 7 float4
 // per node and the per-lane link stack has 16 slots (13 usable: the branch-free pushes of a step may
 // write 3 above the top); else nodes come from global memory at 8 float4 and the stack has 32 (29).
@@ -76,28 +76,15 @@ __global__ __launch_bounds__(kBlock) void k_iow_trace(IowScene S, int leaf_batch
     }
 }
 
-constexpr uint32_t kIowTraceRounds = 16;  // measured on C2: 1 -> 5.5, 4 -> 20.9, 16 -> 32.6 G primary queries/s
-
 namespace {
 template <bool ANY, bool LN>
 int trace_blocks() {  // resident blocks per CU, asked once
-    static const int nb = [] {
-        int n = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_iow_trace<ANY, LN>, kBlock, 0);
-        return (e == hipSuccess && n > 0) ? n : 2;
-    }();
+    static const int nb = occupancy_of(k_iow_trace<ANY, LN>, kBlock);
     return nb;
 }
 template <bool ANY, bool LN>
 hipError_t trace_info(int info[4]) {
-    hipFuncAttributes a;
-    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_iow_trace<ANY, LN>));
-    if (e != hipSuccess) return e;
-    info[0] = a.numRegs;
-    info[1] = (int)a.localSizeBytes;
-    info[2] = (int)a.sharedSizeBytes;
-    info[3] = trace_blocks<ANY, LN>();
-    return hipSuccess;
+    return kernel_info(k_iow_trace<ANY, LN>, trace_blocks<ANY, LN>(), info);
 }
 }  // namespace
 
@@ -116,19 +103,14 @@ hipError_t launch_iow_trace(const IowScene &sc, int leaf_batch, const float4 *ra
     const hipError_t e = hipMemsetAsync(queue, 0, sizeof(unsigned), s);
     if (e != hipSuccess) return e;
     const bool ln = iow_lds(sc);
-    const uint32_t need = (n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
-    const uint32_t cap = (uint32_t)(cus > 0 ? cus : 1) * (uint32_t)iow_trace_blocks_per_cu(any, ln);
-    const dim3 g(need < cap ? need : cap), b(kBlock);
-    // queries per claim: as many 64s as leave every wave of the grid at least four claims (the tail
-    // of a batch stays balanced; a small batch claims 64 at a time)
-    const uint32_t per_wave = n_rays / (64u * g.x * (uint32_t)(kBlock / 64) * 4u);
-    const uint32_t rounds = per_wave < 1u ? 1u : (per_wave > kIowTraceRounds ? kIowTraceRounds : per_wave);
+    const ClaimGrid cg = claim_grid(n_rays, cus, iow_trace_blocks_per_cu(any, ln), 0);
+    const dim3 g(cg.grid), b(kBlock);
     if (any) {
-        if (ln) hipLaunchKernelGGL((k_iow_trace<true, true>), g, b, 0, s, sc, leaf_batch, rays, n_rays, hits, counters, queue, rounds);
-        else hipLaunchKernelGGL((k_iow_trace<true, false>), g, b, 0, s, sc, leaf_batch, rays, n_rays, hits, counters, queue, rounds);
+        if (ln) hipLaunchKernelGGL((k_iow_trace<true, true>), g, b, 0, s, sc, leaf_batch, rays, n_rays, hits, counters, queue, cg.rounds);
+        else hipLaunchKernelGGL((k_iow_trace<true, false>), g, b, 0, s, sc, leaf_batch, rays, n_rays, hits, counters, queue, cg.rounds);
     } else {
-        if (ln) hipLaunchKernelGGL((k_iow_trace<false, true>), g, b, 0, s, sc, leaf_batch, rays, n_rays, hits, counters, queue, rounds);
-        else hipLaunchKernelGGL((k_iow_trace<false, false>), g, b, 0, s, sc, leaf_batch, rays, n_rays, hits, counters, queue, rounds);
+        if (ln) hipLaunchKernelGGL((k_iow_trace<false, true>), g, b, 0, s, sc, leaf_batch, rays, n_rays, hits, counters, queue, cg.rounds);
+        else hipLaunchKernelGGL((k_iow_trace<false, false>), g, b, 0, s, sc, leaf_batch, rays, n_rays, hits, counters, queue, cg.rounds);
     }
     return hipGetLastError();
 }
