@@ -328,6 +328,59 @@ void rt_dev_scene_free(rt_dev_scene *s);
  * RT_E_ARG until a later update succeeds. */
 int rt_dev_scene_inw_update(rt_dev_scene *s, const float *geom, uint32_t n, const float *nodes, const float *aabbs,
                             const float *lights, uint32_t n_lights, double timing_ms[4]);
+/* rt_dev_scene_inw_update with nodes = NULL for inputs that live on the scene's device: the redraw of a
+ * host that moves its objects on the GPU (a torch simulation step, or any producer that keeps the N*28
+ * records in device memory) runs device to device, records -> update -> frame.  d_geom: N*28 records of
+ * the scene's layout; d_aabbs: N*6 boxes (the caller's, or rt_inw_swept_boxes_async's); d_lights: the
+ * layout-4 light SSBO (L*7).  All device pointers; d_geom is read fastest when 16-byte aligned.
+ * The inputs are read in `stream` order (a producer kernel enqueued on `stream` before the call needs no
+ * synchronisation) and all device work runs on `stream`, which the call synchronises (the builds read
+ * counts back; the device is synchronised first, as by rt_dev_scene_inw_update).  When it returns all
+ * of its device work has finished, the derived compact and quantised nodes included, so a render or
+ * query on any stream may follow at once.  No geometry byte crosses to the host, except where the
+ * host builders are needed: a device build that runs past its level cap (rt_debug_wide_info info[7] =
+ * 2 then), a scene with inw_device_build = 0, or one object; then the records and the device LBVH are
+ * copied back once and the host builders run as for rt_dev_scene_inw_update, time-bin trees included.
+ * It builds everything rt_dev_scene_inw_update builds -- the hot, cold and sphere records (byte-equal
+ * to the host's), the lights, the LBVH, leaf boxes, ranks, high-water mark and swept wide tree, the RI
+ * grid, the compact and quantised nodes -- and, new, the time-bin trees (rt_options.inw_time_bins of
+ * the scene) on the device, so the updated scene has every structure a fresh one has.  The decisions
+ * follow the host's rules, from a reduction on the device: sphere records where every object is an
+ * unrotated sphere; the wide walk where no object sticks out of its box by more than the margin and
+ * every value is finite; bin trees where the wide walk applies, inw_time_bins >= 2, some object moves
+ * and every bin box is finite.  Trees that together would reach 2^24 nodes or 2^32 bytes (the walkers'
+ * ids) are not built: the scene keeps the swept tree alone.  A textured object on a scene with no
+ * texture bound cannot be refused up front here: the update succeeds and every render and shading query of
+ * the scene returns RT_E_UNSUPPORTED until a later update.  Frames and queries are bit-identical to a
+ * fresh scene's of the same records and boxes.
+ * flags: 0 is the library's choice, RT_UPDATE_BINS -- the smaller update + frame sum on the C3 scene
+ * (measured, DESIGN.md §5.15: the bin trees raise the update from 1.10 to 2.35 ms and cut the 1920 x
+ * 1080, 500 spp frame that follows from 148.04 to 146.30 ms; the sums, 148.63 [148.05, 148.86] against
+ * 149.12 [148.73, 149.82] ms, lie outside each other's spread; at 200,000 objects 15.9 against 6.9 ms
+ * buys 49 ms of a 2.9 s frame; a host that redraws small or low-sample frames may prefer
+ * RT_UPDATE_NO_BINS); RT_UPDATE_BINS or RT_UPDATE_NO_BINS forces one; both together, or any other bit, is
+ * RT_E_ARG.
+ * timing_ms (may be NULL) receives the host time of {records and decisions; LBVH; swept tree + RI grid +
+ * derived nodes (or the host build); time-bin trees}.
+ * RT_E_ARG for a null scene, null d_geom or d_aabbs, n == 0, null d_lights with n_lights > 0 on a
+ * layout-4 scene or bad flags, and RT_E_UNSUPPORTED for an IOW-03 scene or n > 2^24, come back before a
+ * device is touched, the scene untouched and timing_ms unwritten.  A later failure leaves the scene
+ * broken as rt_dev_scene_inw_update does. */
+#define RT_UPDATE_BINS    4   /* build the time-bin trees (rt_options.inw_time_bins of the scene) */
+#define RT_UPDATE_NO_BINS 8   /* swept tree only, as rt_dev_scene_inw_update's device build leaves it */
+int rt_dev_scene_inw_update_device(rt_dev_scene *s, const float *d_geom /* N*28, device */, uint32_t n,
+                                   const float *d_aabbs /* N*6, device */,
+                                   const float *d_lights /* L*7, device; layout 4 */, uint32_t n_lights,
+                                   int flags, void *stream, double timing_ms[4]);
+/* Per object a box (lo xyz, hi xyz) that contains it over the whole shutter interval, from the records
+ * alone, so a simulation that only moves positions can feed the update without computing boxes: the
+ * segment of its centre from position - delta to position, widened by the object's half extent under
+ * both orientation conventions of its rotation, inflated and rounded outward (the time-bin trees' box
+ * formula with one bin).  These are not rt_pack_inw's boxes: that packer works from the description's
+ * Euler angles and last_position, which the records do not carry.  The image of a scene updated with
+ * them is the reference's image for the LBVH over these boxes.  Device pointers; never synchronises.
+ * RT_E_ARG for null pointers; n == 0 returns RT_OK. */
+int rt_inw_swept_boxes_async(const float *d_geom, uint32_t n, float *d_aabbs_out /* N*6 */, void *stream);
 /* The next edit of an IOW-03 scene (the reference's stage is an editor: every ImGui edit of an object
  * runs CopyObjBuffer and restarts the spiral, 03_Shadows_and_Materials/materials.cpp:77-152, :329-364)
  * on the scene's existing device buffers: new hot and cold records, the RI priors, the object boxes and

@@ -174,7 +174,14 @@ int rt_debug_inw_stick_out(const float *geom, uint32_t n, const float *nodes, co
 #define RT_WALK_RI_IDS   6  /* uint32 object ids; info = {bytes, ids} */
 #define RT_WALK_RI_FRAME 7  /* float lo[3], hi[3], inv[3], int32 dim[3] as the kernels get them; info = {bytes} */
 #define RT_WALK_WBOUND   8  /* one float; info = {bytes} (ranks and dfs_high: rt_debug_wide_info) */
+#define RT_WALK_HOT      9  /* the hot records; info = {bytes, objects, floats per object} */
+#define RT_WALK_COLD    10  /* the cold records; info = {bytes, objects, floats per object} */
+#define RT_WALK_SPH     11  /* the sphere records (size 0 unless every object is an unrotated sphere); info as above */
 int rt_debug_walk_dump(rt_dev_scene *s, int what, void *out, size_t cap_bytes, uint64_t info[8]);
+/* {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of the kernels of
+ * rt_dev_scene_inw_update_device and rt_inw_swept_boxes_async: k_inw_prepare (which = 0), k_bin_boxes (1),
+ * k_swept_boxes (2), k_bin_place (3). */
+int rt_debug_update_kernel(int which, int info[4]);
 /* The host builders' full output, no device: rtamd::inw_wide_build and ri_grid_build over the
  * reference's LBVH nodes ((2n-1) x 8).  info = {wide nodes, dfs_high, wide depth, RI grid built, RI
  * cells, RI ids, wbound as float bits, 0} (zeros when the LBVH is not walkable).  Every array may be

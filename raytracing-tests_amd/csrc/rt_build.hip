@@ -10,6 +10,9 @@
 //     kernels walk, one level per launch, numbered breadth first (top levels first: the LDS
 //     staging takes the first nodes);
 //   - the surrounding-RI grid (counts, scan, fill).
+// An update from device-resident records (rt_dev_scene_inw_update_device) also gets its
+// hot, cold and sphere records and its decisions here (k_inw_prepare) and the time-bin trees: K more
+// runs of the same SAH levels and collapse over k_bin_boxes' boxes, laid out by k_bin_place.
 // The same SAH levels and collapse build the IOW-03 culling BVH of a scene update
 // (iow_cull_build_device) over boxes made from the hot records (k_iow_boxes).
 // The host path (rtamd::inw_wide_build: a full-sweep SAH) stays for fresh scenes; binned with 32
@@ -901,6 +904,296 @@ hipError_t inw_compact_wnodes(const float4 *wnodes, uint32_t nw, float4 *cnodes,
     if (!nw) return hipSuccess;
     hipLaunchKernelGGL(k_compact_wnodes, dim3(nblk(nw * 7u)), dim3(kB), 0, s, wnodes, nw, cnodes);
     return hipGetLastError();
+}
+
+// ---- scene update from device-resident records (rt_dev_scene_inw_update_device)
+namespace {
+
+// A block's records (up to kB of 28 floats) staged in LDS: the block reads its 28-KB run of the record
+// array as consecutive float4 (whole lines; consecutive floats when the caller's pointer is not 16-B
+// aligned), then every lane takes its own record from LDS.  The odd stride spreads a wave's lanes over
+// the banks.
+constexpr int kRecPad = 29;
+__device__ __forceinline__ void stage_records(const float *geom, uint32_t n, float *s_rec) {
+    const uint32_t first = blockIdx.x * kB, cnt = min((uint32_t)kB, n - first);
+    const float *src = geom + (size_t)first * 28;
+    if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0u) {  // uniform
+        const float4 *src4 = reinterpret_cast<const float4 *>(src);
+        for (uint32_t i = threadIdx.x; i < cnt * 7u; i += kB) {
+            const float4 v = src4[i];
+            const uint32_t r = i / 7u;
+            float *o = s_rec + r * kRecPad + 4u * (i - 7u * r);
+            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+        }
+    } else {
+        for (uint32_t i = threadIdx.x; i < cnt * 28u; i += kB) s_rec[(i / 28u) * kRecPad + i % 28u] = src[i];
+    }
+    __syncthreads();
+}
+
+// the words k_inw_prepare reduces (dec[0]; dec[2..3] hold the stick-out maximum, a non-negative double
+// whose bits order as a uint64)
+constexpr uint32_t kDecNotSpheres = 1u, kDecMoving = 2u, kDecTextured = 4u, kDecNonFinite = 8u, kDecBinNonFinite = 16u;
+
+// Records and decisions: the hot, cold and sphere records of every object by the statements of
+// inw_records / inw_sphere_records (rt_scene_build.hip) in their order -- plain IEEE operations under
+// -ffp-contract=off with the correctly rounded divide, so the bytes equal the host's -- and the
+// update's decisions: all spheres, any delta not zero, any TextureIndex >= 1, rtamd::inw_stick_out's
+// maximum over the caller's boxes (its float64 expression; +inf where it meets a value that is not
+// finite) and whether rtamd::inw_bin_boxes would refuse an extent.  A wave folds its lanes, a block
+// its waves, one atomic per block and word.
+__global__ __launch_bounds__(kB) void k_inw_prepare(const float *geom, const float *aabbs, uint32_t n, int layout,
+                                                    float4 *hot, float4 *cold, float4 *sph, uint32_t *dec) {
+    __shared__ float s_rec[kB * kRecPad];
+    __shared__ uint32_t s_fl[kB / 64];
+    __shared__ double s_worst[kB / 64];
+    stage_records(geom, n, s_rec);
+    const uint32_t j = blockIdx.x * kB + threadIdx.x;
+    uint32_t fl = 0u;
+    double worst = 0.0;
+    if (j < n) {
+        float f[28];
+        for (int k = 0; k < 28; k++) f[k] = s_rec[threadIdx.x * kRecPad + k];
+        bool ident = true;  // the rotation exactly the identity (entries 1 and +-0)
+        for (int k = 0; k < 9; k++) ident = ident && f[3 + k] == ((k % 4) == 0 ? 1.0f : 0.0f);
+        const float ri = layout == 4 ? f[19] : f[20];
+        float is[3], is2[3];
+        for (int k = 0; k < 3; k++) {
+            is[k] = 1.0f / f[12 + k];
+            is2[k] = 1.0f / (f[12 + k] * f[12 + k]);
+        }
+        const float type = ident && (f[18] == 1.0f || f[18] == 2.0f) ? f[18] + 0.5f : f[18];
+        float4 *h = hot + (size_t)j * (kInwHot / 4);
+        h[0] = make_float4(f[0], f[1], f[2], f[3]);
+        h[1] = make_float4(f[4], f[5], f[6], f[7]);
+        h[2] = make_float4(f[8], f[9], f[10], f[11]);
+        h[3] = make_float4(f[12], f[13], f[14], f[15]);
+        h[4] = make_float4(f[16], f[17], type, f[19]);
+        h[5] = make_float4(is[0], is[1], is[2], is2[0]);
+        h[6] = make_float4(is2[1], is2[2], ri, 0.0f);
+        float4 *c = cold + (size_t)j * (kInwCold / 4);
+        if (layout == 1) {
+            c[0] = make_float4(f[21], f[22], f[23], f[24]);
+            c[1] = make_float4(f[25], f[26], f[27], f[20]);
+        } else {
+            const float ti = f[27] + 0.1f;
+            const uint32_t tu = ti <= 0.0f ? 0u : (ti >= 4294967040.0f ? 0xffffffffu : (uint32_t)ti);
+            c[0] = make_float4(f[20], f[21], f[22], f[23]);
+            c[1] = make_float4(f[24], f[25], f[26], __uint_as_float(tu));
+            if (ti >= 1.0f) fl |= kDecTextured;
+        }
+        float4 *o = sph + (size_t)j * 3;
+        o[0] = make_float4(f[0], f[1], f[2], is[0]);
+        o[1] = make_float4(f[15], f[16], f[17], ri);
+        o[2] = make_float4(is2[0], is2[1], is2[2], f[19]);
+        if ((int)(f[18] + 0.1f) != 1 || !(f[12] == f[13] && f[13] == f[14]) || !isfinite(f[12]) || !ident)
+            fl |= kDecNotSpheres;
+        if (f[15] != 0.0f || f[16] != 0.0f || f[17] != 0.0f) fl |= kDecMoving;
+        // rtamd::inw_stick_out over the caller's box, and inw_bin_boxes' extent test
+        const float *b = aabbs + (size_t)j * 6;
+        float bx[6];
+        for (int k = 0; k < 6; k++) bx[k] = b[k];
+        const bool cuboid = (int)(f[18] + 0.1f) == 2;
+        double big = 1.0;
+        for (int k = 0; k < 6; k++) big = fmax(big, fabs((double)bx[k]));
+        const double margin = (double)rtamd::kInwStickOut * big;
+        bool bad = false;
+        for (int a = 0; a < 3 && !bad; a++) {
+            double e = 0.0;
+            for (int cc = 0; cc < 3; cc++) {
+                const double x = (double)f[3 + 3 * cc + a] * (double)f[12 + cc];
+                e += cuboid ? 0.5 * fabs(x) : x * x;
+            }
+            if (!cuboid) e = sqrt(e);
+            const double c1 = (double)f[a], c0 = c1 - (double)f[15 + a];
+            const double out = fmax((double)bx[a] - (fmin(c0, c1) - e), (fmax(c0, c1) + e) - (double)bx[3 + a]);
+            if (!isfinite(c0) || !isfinite(c1) || !isfinite(e) || isnan(bx[a]) || isnan(bx[3 + a]) || isnan(out)) bad = true;
+            else worst = fmax(worst, out / margin);
+        }
+        if (bad) {
+            worst = (double)__builtin_huge_valf();
+            fl |= kDecNonFinite;
+        }
+        for (int a = 0; a < 3; a++) {
+            double row = 0.0, col = 0.0;
+            for (int cc = 0; cc < 3; cc++) {
+                const double x = (double)f[3 + 3 * a + cc] * f[12 + cc], y = (double)f[3 + 3 * cc + a] * f[12 + cc];
+                row += x * x;
+                col += y * y;
+            }
+            if (!isfinite(sqrt(fmax(row, col)))) fl |= kDecBinNonFinite;
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        fl |= (uint32_t)__shfl_xor((int)fl, off, 64);
+        worst = fmax(worst, __shfl_xor(worst, off, 64));
+    }
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    if (lane == 0u) { s_fl[wv] = fl; s_worst[wv] = worst; }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        for (uint32_t w = 1; w < kB / 64; w++) { fl |= s_fl[w]; worst = fmax(worst, s_worst[w]); }
+        if (fl) atomicOr(dec, fl);
+        atomicMax(reinterpret_cast<unsigned long long *>(dec + 2), (unsigned long long)__double_as_longlong(worst));
+    }
+}
+
+// rtamd::inw_bin_boxes' box of one record over the time ratios [r0, r1]: the centre segment widened by
+// the half extent under both orientation conventions, inflated, rounded outward to float (its
+// float64 expression, statement by statement)
+__device__ __forceinline__ void bin_box(const float *f, double r0, double r1, float *bx) {
+    double lo[3], hi[3];
+    float big = 0.0f;
+    for (int a = 0; a < 3; a++) {
+        double row = 0.0, col = 0.0;
+        for (int c = 0; c < 3; c++) {
+            const double x = (double)f[3 + 3 * a + c] * f[12 + c], y = (double)f[3 + 3 * c + a] * f[12 + c];
+            row += x * x;
+            col += y * y;
+        }
+        const double e = sqrt(fmax(row, col));
+        const double c0 = (double)f[a] - (double)f[15 + a] * (1.0 - r0);
+        const double c1 = (double)f[a] - (double)f[15 + a] * (1.0 - r1);
+        lo[a] = fmin(c0, c1) - e;
+        hi[a] = fmax(c0, c1) + e;
+        big = fmaxf(big, (float)fmax(fabs(lo[a]), fabs(hi[a])));
+    }
+    for (int a = 0; a < 3; a++) {
+        const double e = (hi[a] - lo[a]) * 1e-3 + 1e-3 + (double)big * 1e-5;
+        bx[a] = f32_down(lo[a] - e);
+        bx[3 + a] = f32_up(hi[a] + e);
+    }
+}
+
+// time bin [r0, r1]: every object's box into the SAH build's box / cen / ids, the largest |coordinate|
+// into meta[3] (as k_leaves)
+__global__ __launch_bounds__(kB) void k_bin_boxes(const float *geom, uint32_t n, double r0, double r1, float *box,
+                                                  float *cen, uint32_t *ids, uint32_t *meta) {
+    __shared__ float s_rec[kB * kRecPad];
+    stage_records(geom, n, s_rec);
+    const uint32_t j = blockIdx.x * kB + threadIdx.x;
+    float wb = 0.0f;
+    if (j < n) {
+        float bx[6];
+        bin_box(s_rec + threadIdx.x * kRecPad, r0, r1, bx);
+        for (int k = 0; k < 3; k++) {
+            box[6 * j + k] = bx[k];
+            box[6 * j + 3 + k] = bx[3 + k];
+            cen[3 * j + k] = 0.5f * (bx[k] + bx[3 + k]);
+            wb = fmaxf(wb, fmaxf(fabsf(bx[k]), fabsf(bx[3 + k])));
+        }
+        ids[j] = j;
+    }
+    for (int off = 32; off >= 1; off >>= 1) wb = fmaxf(wb, __shfl_xor(wb, off, 64));
+    if ((threadIdx.x & 63u) == 0u) atomicMax(meta + 3, __float_as_uint(wb));  // non-negative: uint order = value order
+}
+
+// the whole shutter interval as one bin: the boxes rt_inw_swept_boxes_async writes
+__global__ __launch_bounds__(kB) void k_swept_boxes(const float *geom, uint32_t n, float *out) {
+    __shared__ float s_rec[kB * kRecPad];
+    stage_records(geom, n, s_rec);
+    const uint32_t j = blockIdx.x * kB + threadIdx.x;
+    if (j >= n) return;  // no cross-lane work after the staging
+    float bx[6];
+    bin_box(s_rec + threadIdx.x * kRecPad, 0.0, 1.0, bx);
+    for (int k = 0; k < 6; k++) out[6 * (size_t)j + k] = bx[k];
+}
+
+// The bin trees into the scene's node array (rtamd::inw_wide_add_bins' layout): tree b, built with
+// links of its own at tmp + b * n nodes, goes to node n0 + b * stride with its node links rebased to
+// the whole array; the slots of a tree's stride past its nodes become empty nodes (planes 1e30, links 1e9).
+struct BinTrees { uint32_t nw[16]; };
+__global__ __launch_bounds__(kB) void k_bin_place(const float4 *tmp, uint32_t n, uint32_t bins, uint32_t stride,
+                                                  uint32_t n0, BinTrees t, float4 *wnodes) {
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    if (i >= bins * stride * 10u) return;  // no cross-lane work in this kernel
+    const uint32_t node = i / 10u, r = i - 10u * node, b = node / stride, k = node - b * stride;
+    float4 v;
+    if (k >= t.nw[b]) {
+        const float e = r < 9u ? 1e30f : __int_as_float(1000000000);
+        v = make_float4(e, e, e, e);
+    } else {
+        v = tmp[((size_t)b * n + k) * 10 + r];
+        if (r == 9u) {
+            const int base = (int)(n0 + b * stride);
+            int lk[4] = {__float_as_int(v.x), __float_as_int(v.y), __float_as_int(v.z), __float_as_int(v.w)};
+            for (int c = 0; c < 4; c++)
+                if (lk[c] > 0 && (uint32_t)lk[c] <= t.nw[b]) lk[c] += base;
+            v = make_float4(__int_as_float(lk[0]), __int_as_float(lk[1]), __int_as_float(lk[2]), __int_as_float(lk[3]));
+        }
+    }
+    wnodes[(size_t)(n0 + node) * 10 + r] = v;
+}
+
+}  // namespace
+
+hipError_t inw_prepare_device(const float *geom, const float *aabbs, uint32_t n, int layout, float *hot, float *cold,
+                              float *sph, uint32_t *dec, hipStream_t s) {
+    if (!geom || !aabbs || !n || !hot || !cold || !sph || !dec) return hipErrorInvalidValue;
+    BUILD_HIP(hipMemsetAsync(dec, 0, 8 * 4, s));
+    hipLaunchKernelGGL(k_inw_prepare, dim3(nblk(n)), dim3(kB), 0, s, geom, aabbs, n, layout, reinterpret_cast<float4 *>(hot),
+                       reinterpret_cast<float4 *>(cold), reinterpret_cast<float4 *>(sph), dec);
+    return hipGetLastError();
+}
+
+InwDecisions inw_decisions(const uint32_t dec[8]) {
+    InwDecisions d{};
+    d.spheres = !(dec[0] & kDecNotSpheres);
+    d.moving = (dec[0] & kDecMoving) != 0u;
+    d.textured = (dec[0] & kDecTextured) != 0u;
+    d.bins_finite = !(dec[0] & kDecBinNonFinite);
+    const uint64_t bits = (uint64_t)dec[2] | ((uint64_t)dec[3] << 32);
+    d.stick_out = __builtin_bit_cast(double, bits);
+    return d;
+}
+
+hipError_t inw_swept_boxes_device(const float *geom, uint32_t n, float *out, hipStream_t s) {
+    if (!n) return hipSuccess;
+    if (!geom || !out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_swept_boxes, dim3(nblk(n)), dim3(kB), 0, s, geom, n, out);
+    return hipGetLastError();
+}
+
+hipError_t inw_bin_trees_device(const float *geom, uint32_t n, uint32_t bins, void *ws, size_t ws_bytes, float4 *tmp,
+                                InwBinsDev &out, hipStream_t s, int max_levels) {
+    if (n < 2 || bins < 2 || bins > 16 || !geom || !ws || ws_bytes < inw_build_workspace_bytes(n) || !tmp)
+        return hipErrorInvalidValue;
+    BuildWs w;
+    carve(ws, n, &w);
+    out.stride = 0;
+    out.wbound = 0.0f;
+    for (uint32_t b = 0; b < bins; b++) {
+        BUILD_HIP(build_begin(w, s));
+        hipLaunchKernelGGL(k_bin_boxes, dim3(nblk(n)), dim3(kB), 0, s, geom, n, double(b) / bins, double(b + 1) / bins,
+                           w.box, w.cen, w.ids, w.meta);
+        BUILD_HIP(hipGetLastError());
+        BuildLevels r;
+        BUILD_HIP(build_levels<10>(w, n, tmp + (size_t)b * n * 10, level_cap(max_levels), s, r));
+        out.nw[b] = r.meta[1];
+        out.stride = std::max(out.stride, r.meta[1]);
+        out.wbound = std::max(out.wbound, __builtin_bit_cast(float, r.meta[3]));
+    }
+    return hipSuccess;
+}
+
+hipError_t inw_bin_place_device(const float4 *tmp, uint32_t n, uint32_t bins, const InwBinsDev &t, uint32_t n0,
+                                float4 *wnodes, hipStream_t s) {
+    if (!tmp || !wnodes || bins < 2 || bins > 16 || !t.stride) return hipErrorInvalidValue;
+    BinTrees bt{};
+    for (uint32_t b = 0; b < bins; b++) bt.nw[b] = t.nw[b];
+    hipLaunchKernelGGL(k_bin_place, dim3(nblk((size_t)bins * t.stride * 10)), dim3(kB), 0, s, tmp, n, bins, t.stride, n0, bt,
+                       wnodes);
+    return hipGetLastError();
+}
+
+hipError_t update_kernel_info(int which, int info[4]) {
+    switch (which) {
+        case 0: return kernel_info(k_inw_prepare, occupancy_of(k_inw_prepare, kB), info);
+        case 1: return kernel_info(k_bin_boxes, occupancy_of(k_bin_boxes, kB), info);
+        case 2: return kernel_info(k_swept_boxes, occupancy_of(k_swept_boxes, kB), info);
+        case 3: return kernel_info(k_bin_place, occupancy_of(k_bin_place, kB), info);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 size_t ri_scan_temp_bytes(size_t cells) {

@@ -397,6 +397,31 @@ int rt_dev_scene_inw_update(rt_dev_scene *s, const float *geom, uint32_t n, cons
     }
 }
 
+int rt_dev_scene_inw_update_device(rt_dev_scene *s, const float *d_geom, uint32_t n, const float *d_aabbs,
+                                   const float *d_lights, uint32_t n_lights, int flags, void *stream, double timing_ms[4]) {
+    // argument errors come back before a device is touched, the scene untouched and still valid
+    if (!s || !d_geom || !d_aabbs || n == 0) return RT_E_ARG;
+    if ((flags & ~(RT_UPDATE_BINS | RT_UPDATE_NO_BINS)) || flags == (RT_UPDATE_BINS | RT_UPDATE_NO_BINS)) return RT_E_ARG;
+    if (s->kind != 3 && s->layout == 4 && n_lights > 0 && !d_lights) return RT_E_ARG;
+    if (s->kind == 3 || n > (1u << 24)) return RT_E_UNSUPPORTED;  // (node / object ids are stored as floats, exact to 2^24)
+    HIP_OK(hipSetDevice(s->device));
+    HIP_OK(hipDeviceSynchronize());  // the scene's last frame may still read the buffers being replaced
+    try {  // the host builders of the fallback allocate: no exception crosses the ABI
+        return update_inw_device(s, d_geom, n, d_aabbs, d_lights, n_lights, flags, static_cast<hipStream_t>(stream),
+                                 timing_ms);
+    } catch (...) {
+        s->broken = true;
+        return RT_E_ARG;
+    }
+}
+
+int rt_inw_swept_boxes_async(const float *d_geom, uint32_t n, float *d_aabbs_out, void *stream) {
+    if (!d_geom || !d_aabbs_out) return RT_E_ARG;
+    if (n == 0) return RT_OK;
+    const hipError_t e = rtk::inw_swept_boxes_device(d_geom, n, d_aabbs_out, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RT_OK : launch_failed(e);
+}
+
 int rt_dev_scene_iow03_update(rt_dev_scene *s, const float *types, const float *records, uint32_t n, int flags,
                               double timing_ms[4]) {
     // argument errors come back before a device is touched, the scene untouched and still valid
@@ -795,6 +820,7 @@ int rt_path_rays_async(rt_dev_scene *s, const rt_path_ray *d_rays, uint32_t n_ra
     if (!s || (flags & ~RT_TRACE_INVERT) || max_bounces < 0) return RT_E_ARG;
     if (s->kind == 3) return RT_E_UNSUPPORTED;  // an IOW-03 sample starts from its pixel's previous one
     if (s->broken || n_rays > (1u << 31)) return RT_E_ARG;
+    if (s->tex_missing) return RT_E_UNSUPPORTED;  // a textured object and no texture bound (rt_dev_scene_inw_update_device)
     if (n_rays == 0) return RT_OK;
     if (!d_rays || !d_out) return RT_E_ARG;
     const rtk::InwScene sc = inw_query_view(s);
@@ -888,6 +914,7 @@ int rt_pixel_query_async(rt_dev_scene *s, const rt_camera *cam, const rt_params 
                          size_t ws_bytes, uint64_t *d_counters, void *stream) {
     static_assert(sizeof(rt_pixel_out) == 32, "rt_pixel_out is 2 float4");
     if (!s || !cam || !params_ok(p) || p->spp != s->spp || s->broken) return RT_E_ARG;
+    if (s->tex_missing) return RT_E_UNSUPPORTED;  // a textured object and no texture bound (rt_dev_scene_inw_update_device)
     const uint64_t n = uint64_t(n_pixels) * uint32_t(p->spp);
     if (n > (uint64_t(1) << 31)) return RT_E_ARG;
     if (n_pixels > 0 && (!d_pixels || !d_pixels_out || !d_ws || ws_bytes < pixel_ws_bytes(s, n_pixels))) return RT_E_ARG;
@@ -946,6 +973,7 @@ int rt_render_pass_async(rt_dev_scene *s, const rt_camera *cam, const rt_params 
     static_assert(sizeof(rt_pass_state) == 32, "rt_pass_state is 2 float4");
     if (!s || !cam || !params_ok(p) || !d_state || p->spp != s->spp || s0 >= uint32_t(p->spp) || s->broken)
         return RT_E_ARG;
+    if (s->tex_missing) return RT_E_UNSUPPORTED;  // a textured object and no texture bound (rt_dev_scene_inw_update_device)
     if (p->show_normal) return RT_E_UNSUPPORTED;  // one normal per sample, no fold state
     if (ns == 0) return RT_OK;
     const uint32_t s1 = uint32_t(std::min<uint64_t>(uint64_t(s0) + ns, pass_stop(s)));
@@ -998,6 +1026,7 @@ int rt_render_pass_pixels_async(rt_dev_scene *s, const rt_camera *cam, const rt_
                                 float *d_rgba, float *d_depth, uint64_t *d_counters, void *stream) {
     static_assert(sizeof(rt_pass_aux) == 16, "rt_pass_aux is a float4");
     if (!s || !cam || !params_ok(p) || !d_state || !d_aux || p->spp != s->spp || s->broken) return RT_E_ARG;
+    if (s->tex_missing) return RT_E_UNSUPPORTED;  // a textured object and no texture bound (rt_dev_scene_inw_update_device)
     if (n_pixels > (1u << 31) || (n_pixels > 0 && !d_pixels)) return RT_E_ARG;
     if (p->show_normal) return RT_E_UNSUPPORTED;  // one normal per sample, no fold state
     if (n_pixels == 0 || ns == 0) return RT_OK;

@@ -414,6 +414,9 @@ int rt_debug_walk_dump(rt_dev_scene *s, int what, void *out, size_t cap_bytes, u
         host = &frame; v[0] = w.ri_ok ? sizeof(frame) : 0;
         break;
     case RT_WALK_WBOUND: host = &w.wbound; v[0] = nw ? sizeof(float) : 0; break;
+    case RT_WALK_HOT: src = &s->hot; v[0] = n * rtk::kInwHot * sizeof(float); v[1] = n; v[2] = rtk::kInwHot; break;
+    case RT_WALK_COLD: src = &s->cold; v[0] = n * rtk::kInwCold * sizeof(float); v[1] = n; v[2] = rtk::kInwCold; break;
+    case RT_WALK_SPH: src = &s->sph; v[0] = s->sph_ok ? n * 12 * sizeof(float) : 0; v[1] = s->sph_ok ? n : 0; v[2] = 12; break;
     default: return RT_E_ARG;
     }
     std::memcpy(info, v, sizeof(v));
@@ -533,6 +536,12 @@ int rt_debug_pass_kernel(int which, int info[4]) {
     if (!info || which < 0 || (which > 3 && which < 8) || which > 14) return RT_E_ARG;
     if (which >= 8) HIP_OK(rtk::adaptive_kernel_info(which - 8, info));  // rt_adaptive.hip's
     else HIP_OK(rtk::pass_kernel_info(which, info));
+    return RT_OK;
+}
+
+int rt_debug_update_kernel(int which, int info[4]) {
+    if (!info || which < 0 || which > 3) return RT_E_ARG;
+    HIP_OK(rtk::update_kernel_info(which, info));
     return RT_OK;
 }
 

@@ -60,6 +60,7 @@ struct InwWalk {
                                   // device build ran past its level cap (rt_debug_wide_info info[7])
     DevBuf lbvh_ws, aabb, lcnt;   // rt_dev_scene_inw_update: device LBVH workspace, object boxes, leaf counts
     DevBuf build_ws, ri_fill, ri_tmp;  // ... and the device build of the wide walk and RI grid (rt_build.hip)
+    DevBuf dec, wbin_tmp;         // rt_dev_scene_inw_update_device: k_inw_prepare's decision words, the bin trees as built
     // no structures: the state both builders start from (the buffers keep their capacity)
     void reset() {
         dfs_high = 0;
@@ -163,6 +164,8 @@ struct rt_dev_scene {
     DevBuf walk_ctr;       // the last frame's closest-hit queries handed to the LBVH walks (u64)
     bool broken = false;   // a failed rt_dev_scene_inw_update / rt_dev_scene_iow03_update left the buffers
                            // inconsistent: no renders, no queries
+    bool tex_missing = false;  // rt_dev_scene_inw_update_device met a textured object and the scene has no texture
+                               // bound: renders and queries return RT_E_UNSUPPORTED until a later update
     IowCullPriors iow;
     InwWalk walk;
     InwFold fold;
@@ -278,6 +281,8 @@ int make_inw(rt_dev_scene *s, const float *geom, uint32_t n, int layout, const f
              uint32_t n_lights, const rt_texture *tex, int n_tex, int spp);
 int update_inw(rt_dev_scene *s, const float *geom, uint32_t n, const float *nodes, const float *aabbs,
                const float *lights, uint32_t n_lights, double *ms);
+int update_inw_device(rt_dev_scene *s, const float *d_geom, uint32_t n, const float *d_aabbs, const float *d_lights,
+                      uint32_t n_lights, int flags, hipStream_t st, double *ms);
 int update_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n, int flags, double *ms);
 bool inw_sphere_records(const float *geom, uint32_t n, int layout, std::vector<float> &out);
 bool inw_textured(const float *geom, uint32_t n, int layout);

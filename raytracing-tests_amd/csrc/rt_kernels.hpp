@@ -345,6 +345,39 @@ struct IowCullDev {
 };
 hipError_t iow_cull_build_device(const float *hot, uint32_t n, void *ws, size_t ws_bytes, float4 *wide, float4 *obox,
                                  IowCullDev &out, hipStream_t s, int max_levels = 0);
+// A scene update from device-resident records (rt_build.hip).  None of these synchronises
+// except inw_bin_trees_device (the level counts).
+// inw_prepare_device: the hot (kInwHot floats), cold (kInwCold) and sphere (12) records of the n GeometryBuff
+// records at geom (device, n * 28), byte-equal to inw_records / inw_sphere_records (rt_scene_build.hip), and
+// the decision words dec (8 uint32, device; zeroed here), which inw_decisions decodes once read back.
+struct InwDecisions {
+    bool spheres;      // every object an unrotated sphere (inw_sphere_records returns true)
+    bool moving;       // some delta is not zero
+    bool textured;     // layout 4: some TextureIndex >= 1 (inw_textured)
+    bool bins_finite;  // rtamd::inw_bin_boxes refuses no object
+    double stick_out;  // rtamd::inw_stick_out over the caller's boxes (+inf: some value is not finite)
+};
+hipError_t inw_prepare_device(const float *geom, const float *aabbs, uint32_t n, int layout, float *hot, float *cold,
+                              float *sph, uint32_t *dec, hipStream_t s);
+InwDecisions inw_decisions(const uint32_t dec[8]);
+// per object the box of rtamd::inw_bin_boxes with one bin (n * 6 floats)
+hipError_t inw_swept_boxes_device(const float *geom, uint32_t n, float *out, hipStream_t s);
+// The time-bin trees (rtamd::inw_wide_add_bins) over rtamd::inw_bin_boxes' boxes, computed on the device:
+// tree b built by the SAH and collapse levels into tmp + b * n nodes (10 float4 each) with links of its own,
+// then placed by inw_bin_place_device at node n0 + b * stride of wnodes, links rebased, the rest of each
+// stride empty nodes.  ws holds inw_build_workspace_bytes(n).  hipErrorNotSupported: deeper than max_levels.
+struct InwBinsDev {
+    uint32_t nw[16];  // nodes of each tree
+    uint32_t stride;  // the largest
+    float wbound;     // largest |coordinate| of the bin boxes
+};
+hipError_t inw_bin_trees_device(const float *geom, uint32_t n, uint32_t bins, void *ws, size_t ws_bytes, float4 *tmp,
+                                InwBinsDev &out, hipStream_t s, int max_levels = 0);
+hipError_t inw_bin_place_device(const float4 *tmp, uint32_t n, uint32_t bins, const InwBinsDev &t, uint32_t n0,
+                                float4 *wnodes, hipStream_t s);
+// {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of k_inw_prepare (which = 0), k_bin_boxes
+// (1), k_swept_boxes (2), k_bin_place (3)
+hipError_t update_kernel_info(int which, int info[4]);
 // the quantised form of nw wide nodes (InwScene::qnodes): 4 float4 per node, planes rounded
 // outward by at least `margin` beyond the wide node's (rt_build.hip)
 hipError_t inw_quantize_wnodes(const float4 *wnodes, uint32_t nw, float4 *qnodes, float margin, hipStream_t s);

@@ -286,6 +286,7 @@ int launch_scene_inw_fold(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
 // allocates the chunk workspace; later calls allocate nothing.
 int launch_scene(rt_dev_scene *s, rtk::Frame &f, hipStream_t st) {
     if (s->broken) return RT_E_ARG;  // a failed rt_dev_scene_inw_update (update_inw)
+    if (s->tex_missing) return RT_E_UNSUPPORTED;  // a textured object and no texture bound (update_inw_device)
     f.n_focus = (s->kind != 3 && s->layout == 1) ? s->n_focus : 0;
     std::memcpy(f.focus_list, s->focus, sizeof(f.focus_list));
     f.leaf_batch = s->opt.iow_leaf_batch;

@@ -1,7 +1,7 @@
 // rt_scene_build.hip -- scene construction: converts the reference's record layouts into the
 // kernels' device layouts (hot/cold split, per-object reciprocals hoisted under the numerics
 // contract), builds the sample tables, the walk structures (host and device builds) and the
-// textures, and redoes that per redraw (update_inw, update_iow03).
+// textures, and redoes that per redraw (update_inw, update_inw_device, update_iow03).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -97,17 +97,18 @@ bool inw_wide_ok(const rt_dev_scene *s, const float *geom, uint32_t n, const flo
 // The quantised culling BVH (DESIGN.md §5.2 "Quantised nodes") from the scene's wide nodes, on the
 // device: planes rounded outward by kQMargin beyond the wide nodes' own (the error bound of the
 // walk's decode is below it while every coordinate lies within 1000 of the origin, the fused
-// cull's condition, which the launch checks per frame).  The two kernels run on the null stream;
-// the wait at the end makes the derived nodes complete before any caller returns the scene, so a
-// render enqueued at once on a non-blocking stream reads finished nodes.
+// cull's condition, which the launch checks per frame).  The two kernels run on `st` (the null stream
+// for every entry point but rt_dev_scene_inw_update_device); the wait at the end makes the derived
+// nodes complete before any caller returns the scene, so a render enqueued at once on a non-blocking
+// stream reads finished nodes.
 constexpr float kQMargin = 2e-3f;
-int make_qnodes(InwWalk &w) {
+int make_qnodes(InwWalk &w, hipStream_t st = nullptr) {
     if (!w.n_wnodes) return RT_OK;
     HIP_OK(w.cnodes.reserve(size_t(w.n_wnodes) * 7 * sizeof(float4)));
-    HIP_OK(rtk::inw_compact_wnodes(w.wnodes.as<float4>(), w.n_wnodes, w.cnodes.as<float4>(), nullptr));
+    HIP_OK(rtk::inw_compact_wnodes(w.wnodes.as<float4>(), w.n_wnodes, w.cnodes.as<float4>(), st));
     HIP_OK(w.qnodes.reserve(size_t(w.n_wnodes) * rtk::kQNodeF4 * sizeof(float4)));
-    HIP_OK(rtk::inw_quantize_wnodes(w.wnodes.as<float4>(), w.n_wnodes, w.qnodes.as<float4>(), kQMargin, nullptr));
-    HIP_OK(hipStreamSynchronize(nullptr));
+    HIP_OK(rtk::inw_quantize_wnodes(w.wnodes.as<float4>(), w.n_wnodes, w.qnodes.as<float4>(), kQMargin, st));
+    HIP_OK(hipStreamSynchronize(st));
     return RT_OK;
 }
 
@@ -160,51 +161,65 @@ int make_inw_wide(rt_dev_scene *s, const float *nodes, uint32_t n, bool wide, do
 }
 
 // The same structures built on the device from the scene's device LBVH (rt_build.hip, DESIGN.md
-// "Device build"; rt_options.inw_device_build): no host build, no upload.  ms: host wall time of
-// the build (its level loop and the RI grid read counts back) in ms[0], 0 in ms[1].
-int make_inw_wide_device(rt_dev_scene *s, uint32_t n, bool wide, double *ms) {
+// "Device build"; rt_options.inw_device_build): no host build, no upload.  Two steps, both on `st`:
+// the swept tree, ranks, leaf boxes and high-water mark (RT_E_UNSUPPORTED: deeper than the level cap,
+// the caller builds on the host), then, for a scene that takes the wide walk, the RI grid and the
+// walk's counts (the derived nodes follow: make_qnodes).
+int inw_swept_build_device(rt_dev_scene *s, uint32_t n, rtk::InwWideDev &out, hipStream_t st) {
     InwWalk &d = s->walk;
-    d.reset();
-    const auto t0 = std::chrono::steady_clock::now();
     HIP_OK(d.wnodes.reserve(size_t(n) * 40 * sizeof(float)));
     HIP_OK(d.wrank.reserve(size_t(n) * 2 * sizeof(uint32_t)));
     HIP_OK(d.wleaf.reserve(size_t(n) * 8 * sizeof(float)));
     const size_t wsb = rtk::inw_build_workspace_bytes(n);
     HIP_OK(d.build_ws.reserve(wsb));
-    rtk::InwWideDev out{d.wnodes.as<float4>(), d.wrank.as<uint32_t>(), d.wleaf.as<float4>(), 0, 0, 0, 0.0f, {}, {}};
-    {
-        const hipError_t be = rtk::inw_wide_build_device(s->nodes.as<float4>(), d.lcnt.as<uint32_t>(), n,
-                                                         d.build_ws.p, d.build_ws.bytes, out, nullptr, g_build_levels);
-        if (be == hipErrorNotSupported) return RT_E_UNSUPPORTED;  // deeper than its level cap: the caller builds on the host
-        HIP_OK(be);
-    }
-    if (wide) {
-        double dlo[3], dhi[3], inv[3];
-        int dim[3];
-        for (int a = 0; a < 3; a++) { dlo[a] = out.ri_lo[a]; dhi[a] = out.ri_hi[a]; }
-        if (rtamd::ri_grid_dims(dlo, dhi, n, dim, inv)) {
-            const size_t nc = size_t(dim[0]) * dim[1] * dim[2];
-            HIP_OK(d.ri_cells.reserve((nc + 1) * sizeof(uint32_t)));
-            const size_t tb = rtk::ri_scan_temp_bytes(nc + 1);
-            HIP_OK(d.ri_tmp.reserve(tb));
-            uint32_t total = 0, over = 0;
-            HIP_OK(rtk::ri_count_device(d.wleaf.as<float4>(), n, d.build_ws.p, dlo, inv, dim, d.ri_cells.as<uint32_t>(),
-                                        d.ri_tmp.p, tb, &total, &over, nullptr));
-            if (!over) {
-                HIP_OK(d.ri_ids.reserve(std::max<size_t>(1, total) * sizeof(uint32_t)));
-                HIP_OK(d.ri_fill.reserve(std::max<size_t>(1, nc) * sizeof(uint32_t)));
-                HIP_OK(rtk::ri_fill_device(d.wleaf.as<float4>(), n, dlo, inv, dim, d.ri_cells.as<uint32_t>(),
-                                           d.ri_fill.as<uint32_t>(), d.ri_ids.as<uint32_t>(), nullptr));
-                for (int a = 0; a < 3; a++) {
-                    d.ri_lo[a] = float(dlo[a]); d.ri_hi[a] = float(dhi[a]); d.ri_inv[a] = float(inv[a]);
-                    d.ri_dim[a] = dim[a];
-                }
-                d.ri_ok = true;
+    out = rtk::InwWideDev{d.wnodes.as<float4>(), d.wrank.as<uint32_t>(), d.wleaf.as<float4>(), 0, 0, 0, 0.0f, {}, {}};
+    const hipError_t be = rtk::inw_wide_build_device(s->nodes.as<float4>(), d.lcnt.as<uint32_t>(), n,
+                                                     d.build_ws.p, d.build_ws.bytes, out, st, g_build_levels);
+    if (be == hipErrorNotSupported) return RT_E_UNSUPPORTED;  // deeper than its level cap: the caller builds on the host
+    HIP_OK(be);
+    return RT_OK;
+}
+int inw_swept_commit_device(rt_dev_scene *s, uint32_t n, const rtk::InwWideDev &out, hipStream_t st) {
+    InwWalk &d = s->walk;
+    double dlo[3], dhi[3], inv[3];
+    int dim[3];
+    for (int a = 0; a < 3; a++) { dlo[a] = out.ri_lo[a]; dhi[a] = out.ri_hi[a]; }
+    if (rtamd::ri_grid_dims(dlo, dhi, n, dim, inv)) {
+        const size_t nc = size_t(dim[0]) * dim[1] * dim[2];
+        HIP_OK(d.ri_cells.reserve((nc + 1) * sizeof(uint32_t)));
+        const size_t tb = rtk::ri_scan_temp_bytes(nc + 1);
+        HIP_OK(d.ri_tmp.reserve(tb));
+        uint32_t total = 0, over = 0;
+        HIP_OK(rtk::ri_count_device(d.wleaf.as<float4>(), n, d.build_ws.p, dlo, inv, dim, d.ri_cells.as<uint32_t>(),
+                                    d.ri_tmp.p, tb, &total, &over, st));
+        if (!over) {
+            HIP_OK(d.ri_ids.reserve(std::max<size_t>(1, total) * sizeof(uint32_t)));
+            HIP_OK(d.ri_fill.reserve(std::max<size_t>(1, nc) * sizeof(uint32_t)));
+            HIP_OK(rtk::ri_fill_device(d.wleaf.as<float4>(), n, dlo, inv, dim, d.ri_cells.as<uint32_t>(),
+                                       d.ri_fill.as<uint32_t>(), d.ri_ids.as<uint32_t>(), st));
+            for (int a = 0; a < 3; a++) {
+                d.ri_lo[a] = float(dlo[a]); d.ri_hi[a] = float(dhi[a]); d.ri_inv[a] = float(inv[a]);
+                d.ri_dim[a] = dim[a];
             }
+            d.ri_ok = true;
         }
-        d.n_wnodes = d.n_wtree0 = out.n_wnodes;
-        d.wdepth = out.depth;
-        d.wbound = out.wbound;
+    }
+    d.n_wnodes = d.n_wtree0 = out.n_wnodes;
+    d.wdepth = out.depth;
+    d.wbound = out.wbound;
+    return RT_OK;
+}
+
+// rt_dev_scene_inw_update's device build: the two steps on the null stream.  ms: host wall time of
+// the build (its level loop and the RI grid read counts back) in ms[0], 0 in ms[1].
+int make_inw_wide_device(rt_dev_scene *s, uint32_t n, bool wide, double *ms) {
+    InwWalk &d = s->walk;
+    d.reset();
+    const auto t0 = std::chrono::steady_clock::now();
+    rtk::InwWideDev out{};
+    if (int rc = inw_swept_build_device(s, n, out, nullptr); rc != RT_OK) return rc;
+    if (wide) {
+        if (int rc = inw_swept_commit_device(s, n, out, nullptr); rc != RT_OK) return rc;
         if (int rc = make_qnodes(d); rc != RT_OK) return rc;
     }
     HIP_OK(hipDeviceSynchronize());  // the build kernels too
@@ -214,6 +229,42 @@ int make_inw_wide_device(rt_dev_scene *s, uint32_t n, bool wide, double *ms) {
         ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         ms[1] = 0.0;
     }
+    return RT_OK;
+}
+
+// The time-bin trees of a device-built scene (rtamd::inw_wide_add_bins' trees and layout, built by
+// rtk::inw_bin_trees_device from the records at d_geom) appended to the swept tree the scene's walk
+// holds.  RT_E_UNSUPPORTED: a tree ran past the level cap (the caller builds on the host).  The scene
+// keeps the swept tree alone (RT_OK) when the trees would not fit the walkers' ids: the buffer-load
+// walk multiplies node ids with __umul24 and counts records in 32 bits, so all trees together stay
+// below 2^24 nodes and 2^32 bytes.
+int add_bins_device(rt_dev_scene *s, const float *d_geom, uint32_t n, uint32_t bins, hipStream_t st) {
+    InwWalk &d = s->walk;
+    constexpr uint64_t kMaxNodes = uint64_t(1) << 24, kMaxBytes = uint64_t(1) << 32, kNodeBytes = 10 * sizeof(float4);
+    auto fits = [&](uint64_t nodes) { return nodes < kMaxNodes && nodes * kNodeBytes < kMaxBytes; };
+    // (a 4-wide tree over n objects has at least (n - 1) / 3 nodes: scenes that cannot fit build nothing)
+    if (!fits(uint64_t(d.n_wtree0) + uint64_t(bins) * ((n - 1) / 3))) return RT_OK;
+    HIP_OK(d.wbin_tmp.reserve(size_t(bins) * n * kNodeBytes));
+    rtk::InwBinsDev t{};
+    const hipError_t be = rtk::inw_bin_trees_device(d_geom, n, bins, d.build_ws.p, d.build_ws.bytes,
+                                                    d.wbin_tmp.as<float4>(), t, st, g_build_levels);
+    if (be == hipErrorNotSupported) return RT_E_UNSUPPORTED;
+    HIP_OK(be);
+    const uint64_t total = uint64_t(d.n_wtree0) + uint64_t(bins) * t.stride;
+    if (!fits(total)) return RT_OK;
+    if (d.wnodes.bytes < total * kNodeBytes) {  // a larger node array that keeps the swept tree (with room to grow)
+        DevBuf grown;
+        HIP_OK(grown.alloc(size_t(total + total / 8) * kNodeBytes));
+        HIP_OK(hipMemcpyAsync(grown.p, d.wnodes.p, size_t(d.n_wtree0) * kNodeBytes, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipStreamSynchronize(st));
+        std::swap(grown.p, d.wnodes.p);
+        std::swap(grown.bytes, d.wnodes.bytes);
+    }
+    HIP_OK(rtk::inw_bin_place_device(d.wbin_tmp.as<float4>(), n, bins, t, d.n_wtree0, d.wnodes.as<float4>(), st));
+    d.n_wnodes = uint32_t(total);
+    d.wbins = bins;
+    d.wbin_stride = t.stride;
+    d.wbound = std::fmax(d.wbound, t.wbound);
     return RT_OK;
 }
 
@@ -537,6 +588,116 @@ int update_inw(rt_dev_scene *s, const float *geom, uint32_t n, const float *node
         d.wbuild = 0;
     }
     if (ms) { ms[2] = w[0]; ms[3] = w[1]; }
+    s->n = n;
+    s->n_lights = nl;
+    s->tex_missing = false;  // (rt_dev_scene_inw_update refuses such records before it gets here)
+    s->broken = false;
+    return RT_OK;
+}
+
+// The library's choice for rt_dev_scene_inw_update_device's flags = 0, from the measured rows of DESIGN.md
+// §5.15 (profiles/update_dev_c3.json): on the C3 scene the bin trees add 1.25 ms to the update (2.35
+// against 1.10 ms) and take 1.74 ms off the frame that follows (146.30 against 148.04 ms), so update +
+// frame is 148.63 [148.05, 148.86] ms with them and 149.12 [148.73, 149.82] ms without; neither median
+// lies inside the other's spread.
+constexpr int kInwUpdateDefault = RT_UPDATE_BINS;
+
+// update_inw with nodes = NULL for records, boxes and lights that live on the scene's device
+// (rt_dev_scene_inw_update_device): the records and the decisions by k_inw_prepare, the LBVH from the
+// caller's boxes, the swept tree, the RI grid, the time-bin trees and the derived nodes, all on `st`;
+// the decision words are read back after the swept build's own reads.  No geometry crosses to the host
+// unless the host builders are needed (the level cap, inw_device_build = 0, one object): then the records
+// and the device LBVH are copied back once and make_inw_wide builds as it does for update_inw.
+// ms[4]: host time of the records and decisions, the LBVH, the swept tree + RI grid + derived nodes
+// (or the host build), the time-bin trees.
+int update_inw_device(rt_dev_scene *s, const float *d_geom, uint32_t n, const float *d_aabbs, const float *d_lights,
+                      uint32_t n_lights, int flags, hipStream_t st, double *ms) {
+    using clk = std::chrono::steady_clock;
+    auto t = clk::now();
+    auto lap = [&]() {
+        const auto now = clk::now();
+        const double v = std::chrono::duration<double, std::milli>(now - t).count();
+        t = now;
+        return v;
+    };
+    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
+    const bool want_bins = (flags ? flags : kInwUpdateDefault) == RT_UPDATE_BINS;
+    s->broken = true;  // (as update_inw: the new sizes are committed at the end)
+    s->sph_ok = false;
+    InwWalk &d = s->walk;
+    const uint32_t nl = s->layout == 4 ? n_lights : 0;
+    HIP_OK(s->hot.reserve(size_t(n) * rtk::kInwHot * sizeof(float)));
+    HIP_OK(s->cold.reserve(size_t(n) * rtk::kInwCold * sizeof(float)));
+    HIP_OK(s->sph.reserve(size_t(n) * 12 * sizeof(float)));
+    HIP_OK(d.dec.reserve(8 * sizeof(uint32_t)));
+    HIP_OK(rtk::inw_prepare_device(d_geom, d_aabbs, n, s->layout, s->hot.as<float>(), s->cold.as<float>(),
+                                   s->sph.as<float>(), d.dec.as<uint32_t>(), st));
+    if (nl) {
+        HIP_OK(s->lights.reserve(size_t(nl) * 7 * sizeof(float)));
+        HIP_OK(hipMemcpyAsync(s->lights.p, d_lights, size_t(nl) * 7 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    if (ms) ms[0] = lap();
+    const bool device_build = s->opt.inw_device_build && n >= 2;
+    const size_t nbytes = size_t(2 * n - 1) * 8 * sizeof(float);
+    HIP_OK(s->nodes.reserve(nbytes));
+    const size_t ws = rtk::lbvh_workspace_bytes(n);
+    HIP_OK(d.lbvh_ws.reserve(ws));
+    if (device_build) HIP_OK(d.lcnt.reserve(size_t(2 * n - 1) * sizeof(uint32_t)));
+    HIP_OK(rtk::lbvh_build_device(d_aabbs, n, s->nodes.as<float>(), d.lbvh_ws.p, ws, st,
+                                  device_build ? d.lcnt.as<uint32_t>() : nullptr));
+    if (ms) ms[1] = lap();
+    d.reset();
+    rtk::InwWideDev out{};
+    bool host_build = !device_build;
+    if (device_build) {
+        const int rc = inw_swept_build_device(s, n, out, st);
+        if (rc == RT_E_UNSUPPORTED) host_build = true;
+        else if (rc != RT_OK) return rc;
+    }
+    uint32_t dec[8];
+    HIP_OK(hipMemcpyAsync(dec, d.dec.p, sizeof(dec), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const rtk::InwDecisions dcs = rtk::inw_decisions(dec);
+    const bool wide = s->opt.inw_wide_walk && n >= 2 && dcs.stick_out <= 1.0;  // inw_wide_ok
+    const uint32_t K = s->opt.inw_time_bins > 1 ? uint32_t(s->opt.inw_time_bins) : 0u;
+    double bins_ms = 0.0;
+    if (!host_build) {
+        if (wide) {
+            if (int rc = inw_swept_commit_device(s, n, out, st); rc != RT_OK) return rc;
+            if (want_bins && K >= 2 && K <= 16 && dcs.moving && dcs.bins_finite) {  // inw_wide_add_bins' conditions
+                const auto tb = clk::now();
+                const int rc = add_bins_device(s, d_geom, n, K, st);
+                if (rc == RT_E_UNSUPPORTED) host_build = true;
+                else if (rc != RT_OK) return rc;
+                bins_ms = std::chrono::duration<double, std::milli>(clk::now() - tb).count();
+            }
+        }
+        if (!host_build) {
+            if (wide)
+                if (int rc = make_qnodes(d, st); rc != RT_OK) return rc;
+            d.dfs_high = out.dfs_high;
+            d.sl_ok = true;  // the device LBVH has the stackless layout by construction (rt_lbvh.hip)
+            d.wbuild = 1;
+        }
+    }
+    if (host_build) {
+        std::vector<float> geom(size_t(n) * 28), host_nodes(nbytes / sizeof(float));
+        HIP_OK(hipMemcpyAsync(geom.data(), d_geom, geom.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(host_nodes.data(), s->nodes.p, nbytes, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        double w[2] = {0.0, 0.0};
+        if (int rc = make_inw_wide(s, host_nodes.data(), n, wide, w, want_bins ? geom.data() : nullptr); rc != RT_OK)
+            return rc;
+        d.wbuild = device_build ? 2 : 0;
+        bins_ms = 0.0;
+    }
+    HIP_OK(hipStreamSynchronize(st));  // every copy and kernel of this call: a render on any stream may follow
+    if (ms) {
+        ms[2] = lap() - bins_ms;
+        ms[3] = bins_ms;
+    }
+    s->sph_ok = dcs.spheres;
+    s->tex_missing = dcs.textured && s->n_tex == 0;  // renders and queries return RT_E_UNSUPPORTED
     s->n = n;
     s->n_lights = nl;
     s->broken = false;

@@ -184,6 +184,9 @@ SIGNATURES = {
     "rt_dev_scene_set_options": (C.c_int, [C.c_void_p, C.POINTER(RtOptions)]),
     "rt_dev_scene_inw_update": (C.c_int, [C.c_void_p, _FP, C.c_uint32, _FP, _FP, _FP, C.c_uint32,
                                           C.POINTER(C.c_double)]),
+    "rt_dev_scene_inw_update_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                 C.c_int, C.c_void_p, C.POINTER(C.c_double)]),
+    "rt_inw_swept_boxes_async": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_dev_scene_iow03_update": (C.c_int, [C.c_void_p, _FP, _FP, C.c_uint32, C.c_int, C.POINTER(C.c_double)]),
     "rt_debug_iow_info": (C.c_int, [C.c_void_p, _U32P]),
     "rt_debug_iow_dump": (C.c_int, [C.c_void_p, _U32P, _FP, _FP]),
@@ -245,6 +248,7 @@ SIGNATURES = {
     "rt_render_passes_iow03": (C.c_int, [_FP, _FP, C.c_uint32, C.POINTER(RtCamera), C.POINTER(RtParams), _U32P,
                                          C.c_int, _FP, C.c_void_p, C.c_int, C.POINTER(RtStats)]),
     "rt_debug_pass_kernel": (C.c_int, [C.c_int, _IP]),
+    "rt_debug_update_kernel": (C.c_int, [C.c_int, _IP]),
     "rt_debug_pass_max_blocks": (C.c_int, [C.c_int]),
     "rt_render_pass_pixels_async": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_void_p,
                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -585,6 +589,7 @@ def iow_host_dump(types: np.ndarray, records: np.ndarray, n: int) -> dict | None
 
 
 RT_UPDATE_HOST_BUILD, RT_UPDATE_DEVICE_BUILD = 1, 2
+RT_UPDATE_BINS, RT_UPDATE_NO_BINS = 4, 8
 
 
 def update_iow03(handle, types: np.ndarray, records: np.ndarray, flags: int = 0) -> list:
@@ -629,6 +634,7 @@ def iow_dump(handle) -> dict | None:
 
 RT_WALK_WNODES, RT_WALK_CNODES, RT_WALK_QNODES, RT_WALK_LEAFBOX, RT_WALK_LBVH = 0, 1, 2, 3, 4
 RT_WALK_RI_CELLS, RT_WALK_RI_IDS, RT_WALK_RI_FRAME, RT_WALK_WBOUND = 5, 6, 7, 8
+RT_WALK_HOT, RT_WALK_COLD, RT_WALK_SPH = 9, 10, 11
 
 
 def walk_dump(scene, what: int, dtype=np.float32):
@@ -645,7 +651,8 @@ def walk_dump(scene, what: int, dtype=np.float32):
 
 def walk_dump_all(scene) -> dict:
     """Every structure rt_debug_walk_dump and rt_debug_wide_info read back, in inw_host_dump's keys plus
-    cnodes (N, 28), qnodes (N, 4 * float4 per node), lbvh (2n-1, 8), n and build (where it was built)."""
+    cnodes (N, 28), qnodes (N, 4 * float4 per node), lbvh (2n-1, 8), n and build (where it was built), and the
+    records the kernels see: hot (n, 28), cold (n, 8), sph (n, 12) or None (not every object is a sphere)."""
     lib = load()
     wi = (C.c_uint32 * 8)()
     check(lib.rt_debug_wide_info(scene, wi, None), "rt_debug_wide_info")
@@ -661,6 +668,9 @@ def walk_dump_all(scene) -> dict:
     ids, _ = walk_dump(scene, RT_WALK_RI_IDS, np.uint32)
     frame, _ = walk_dump(scene, RT_WALK_RI_FRAME)
     wb, _ = walk_dump(scene, RT_WALK_WBOUND)
+    hot, ih = walk_dump(scene, RT_WALK_HOT)
+    cold, icd = walk_dump(scene, RT_WALK_COLD)
+    sph, isp = walk_dump(scene, RT_WALK_SPH)
     ok = int(ic[2])
     return {"n": n, "build": int(wi[7]), "wnodes": wn.reshape(-1, 40), "n_wtree0": iw[2], "wbins": iw[3],
             "wbin_stride": iw[4], "depth": iw[5], "cnodes": cn.reshape(-1, 28),
@@ -669,7 +679,8 @@ def walk_dump_all(scene) -> dict:
             "ri_cells": cells if ok else None, "ri_ids": ids if ok else None,
             "ri_lo": frame[0:3] if ok else None, "ri_hi": frame[3:6] if ok else None,
             "ri_inv": frame[6:9] if ok else None, "ri_dim": frame[9:12].view(np.int32) if ok else None,
-            "wide_info": [int(x) for x in wi]}
+            "wide_info": [int(x) for x in wi], "hot": hot.reshape(-1, max(1, ih[2])),
+            "cold": cold.reshape(-1, max(1, icd[2])), "sph": sph.reshape(-1, max(1, isp[2])) if isp[0] else None}
 
 
 def inw_stick_out(geom: np.ndarray, nodes: np.ndarray | None = None, aabbs: np.ndarray | None = None) -> float:
@@ -1009,6 +1020,35 @@ ADAPTIVE_KERNELS = {8: "k_adapt_rays (INW)", 9: "k_adapt_fold (INW)", 10: "k_iow
 def _dptr(t):
     """A device pointer: None, an integer, or anything with data_ptr() (a torch tensor)."""
     return t.data_ptr() if hasattr(t, "data_ptr") else t
+
+
+def update_inw_device(handle, d_geom, n: int, d_aabbs, d_lights=None, n_lights: int = 0, flags: int = 0,
+                      stream=None) -> list:
+    """rt_dev_scene_inw_update_device: the next frame's geometry of the INW device scene `handle` from
+    device buffers (pointers or torch tensors): d_geom n * 28 records, d_aabbs n * 6 boxes, d_lights the
+    layout-4 lights; flags 0, RT_UPDATE_BINS or RT_UPDATE_NO_BINS.  Returns timing_ms: host ms of [records
+    and decisions, LBVH, swept tree + RI grid + derived nodes, time-bin trees]."""
+    tm = (C.c_double * 4)()
+    check(load().rt_dev_scene_inw_update_device(handle, _dptr(d_geom), int(n), _dptr(d_aabbs), _dptr(d_lights),
+                                                int(n_lights), int(flags), stream, tm),
+          "rt_dev_scene_inw_update_device")
+    return list(tm)
+
+
+def inw_swept_boxes(d_geom, n: int, d_out, stream=None) -> None:
+    """rt_inw_swept_boxes_async: per record of d_geom (n * 28, device) a box that holds the object over
+    the shutter interval into d_out (n * 6, device); pointers or torch tensors."""
+    check(load().rt_inw_swept_boxes_async(_dptr(d_geom), int(n), _dptr(d_out), stream), "rt_inw_swept_boxes_async")
+
+
+UPDATE_KERNELS = ("k_inw_prepare", "k_bin_boxes", "k_swept_boxes", "k_bin_place")
+
+
+def update_kernel_info(which: int) -> dict:
+    """rt_debug_update_kernel: registers, scratch, LDS and resident blocks per CU of UPDATE_KERNELS[which]."""
+    info = (C.c_int * 4)()
+    check(load().rt_debug_update_kernel(int(which), info), "rt_debug_update_kernel")
+    return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
 
 
 def pass_pixels(handle, camera: RtCamera, params: RtParams, d_pixels, n_pixels: int, ns: int, d_state, d_aux,
