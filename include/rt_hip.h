@@ -733,8 +733,9 @@ int rt_pixels_iow03(const float *types, const float *records /* N*24 */, uint32_
  * Returns RT_E_ARG, before a device is touched and with the buffers untouched, for a null scene, cam,
  * p or d_state, bad params as the renders judge them, p->spp != the scene's, s0 >= p->spp or a scene
  * a failed update left broken; then RT_E_UNSUPPORTED for p->show_normal != 0.  ns == 0 returns RT_OK
- * and launches nothing; s0 + ns may overrun S (the pass is clipped).  Not covered: packed tile lists,
- * device groups and the MULTIFOCUS camera (no device scene has one: only rt_render_inw_mf's own).
+ * and launches nothing; s0 + ns may overrun S (the pass is clipped).  Packed tile lists and
+ * device groups are served by rt_render_pass_tiles_async and rt_render_pass_multi_async in the multi-GPU
+ * section.  Not covered: the MULTIFOCUS camera (no device scene has one: only rt_render_inw_mf's own).
  * Packed pixel lists, with a sample count per pixel, are served by rt_render_pass_pixels_async below;
  * "Captured graphs" there states a rule that was seen to hold for captured passes as well. */
 typedef struct rt_pass_state { float acc[3]; float depth; float ri[4]; } rt_pass_state;   /* 32 B */
@@ -876,6 +877,69 @@ int rt_render_multi_async(rt_group *g, rt_dev_scene *const *scenes, const rt_cam
 int rt_render_inw_multi(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
                         uint32_t n_lights, const rt_camera *cam, const rt_params *p, const int *devices, int n_dev,
                         int tile_size, float *rgba, float *depth, rt_stats *st);
+
+/* Progressive sample passes on packed tile lists and on device groups: a host that deals a frame over
+ * several devices shows it after the first few samples, as a single-device host does with
+ * rt_render_pass_async, and ends at the same frame, bit for bit.
+ *
+ * rt_render_pass_tiles_async is rt_render_pass_async over a packed tile list.  Tiles and slots are
+ * rt_render_tiles_async's: tile_size is a positive multiple of 16, d_tiles holds n_tiles (tx, ty) int
+ * pairs, slot = tile * T*T + iy * T + ix, and p->tile_* is ignored.
+ *   - A slot inside the image behaves as its pixel does under rt_render_pass_async with the same s0 and
+ *     ns: samples [s0, min(s0 + ns, S)) with the same S, the state not read at s0 == 0 and left
+ *     byte-equal to that pixel's, the image acc * RN(1 / k) with alpha 1, the depth the state's (INW) or
+ *     0 (IOW-03).
+ *   - A slot outside the image (the ragged right and bottom tiles) runs no path; its state bytes are
+ *     neither read nor written; its image slot is written as (0, 0, 0, 0) and its depth as 0 by every
+ *     pass that is given the buffers, as rt_render_tiles_async writes them.  After the pass that reaches
+ *     S the packed image is byte-equal to rt_render_tiles_async's for the same list, and on an INW scene
+ *     so is the packed depth (an IOW-03 pass writes the depth 0 where the IOW-03 renders write nothing).
+ *   - counters, options, synchronisation and allocation are the passes': [0], [3], [4], [5] (INW) or [0],
+ *     [4], [5] (IOW-03), summed over a frame's passes and a partition's lists, are the render's; the
+ *     scene's options change no bit; it never synchronises; an INW scene grows its pass workspace on
+ *     the first call of a list size, IOW-03 allocates nothing.
+ * Returns RT_E_ARG, before a device is touched and with the buffers untouched, for the passes'
+ * conditions, null d_tiles, n_tiles <= 0, a bad tile_size or n_tiles * T*T > 2^31; then
+ * RT_E_UNSUPPORTED for p->show_normal != 0 or a scene an update left without its textures.
+ * The adaptive calls (pixel lists: rt_render_pass_pixels_async, rt_pass_select_async) stay uncovered on
+ * tile lists and on groups. */
+int rt_render_pass_tiles_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p,
+                               const int *d_tiles, int n_tiles, int tile_size,
+                               uint32_t s0, uint32_t ns,
+                               rt_pass_state *d_state_packed   /* n_tiles*T*T */,
+                               float *d_out_packed             /* n_tiles*T*T*4, may be NULL */,
+                               float *d_out_depth_packed       /* n_tiles*T*T,   may be NULL */,
+                               uint64_t *d_counters            /* may be NULL */, void *stream);
+/* One pass of a group's frame: the deal, the streams and the argument rules are rt_render_multi_async's
+ * (scenes of other devices are refused; a frame or tile size change synchronises before the lists
+ * change).  The group owns one packed state buffer per device, 32 B per slot of the device's share,
+ * allocated with the deal: fold state never leaves its device.  Every device runs
+ * rt_render_pass_tiles_async on its share.  With d_rgba the grouped send / recv brings the packed image,
+ * the depth (when d_depth is given) and the counters to device 0, where the W x H image is unpacked: it
+ * is byte-equal to rt_render_pass_async's image and depth for the same cuts on one device, and after the
+ * last pass to the frame of rt_render_multi_async and rt_render_image_async, on an INW scene depth included
+ * (an IOW-03 pass writes the depth 0 where the IOW-03 renders write nothing).  With d_rgba == NULL only
+ * the counters travel (d_depth is then ignored).
+ * The group remembers how many samples its states hold for the current deal, min(s0 + ns, p->spp) after
+ * a pass: s0 must be 0 (a new frame) or exactly that count, anything else is RT_E_ARG with nothing
+ * launched, as are s0 >= p->spp, bad params, rt_render_multi_async's argument errors and any scene with
+ * another spp or left broken by an update; then RT_E_UNSUPPORTED for p->show_normal or a scene an update
+ * left without its textures.  Every scene is asked before the group is touched: a refused call leaves the
+ * deal, the states and the count as they were.  A changed deal resets the count to 0; rt_render_multi_async calls in between leave
+ * states and count alone; a pass that fails on some device leaves the count at 0.  ns == 0 returns RT_OK
+ * and launches nothing.  Group passes have not been captured into graphs (a group works on several
+ * streams: see "Captured graphs" above). */
+int rt_render_pass_multi_async(rt_group *g, rt_dev_scene *const *scenes, const rt_camera *cam, const rt_params *p,
+                               int tile_size, uint32_t s0, uint32_t ns,
+                               float *d_rgba /* may be NULL */, float *d_depth /* may be NULL */,
+                               uint64_t *d_counters /* may be NULL */, void *stream);
+/* Blocking form: rt_render_inw_multi's scenes and group, rt_render_passes_inw's cuts and images (image i
+ * at rgba + i * W*H*4, depth + i * W*H; depth may be NULL).  RT_E_ARG also for bad cuts or a bad
+ * tile_size. */
+int rt_render_passes_inw_multi(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                               uint32_t n_lights, const rt_camera *cam, const rt_params *p, const int *devices,
+                               int n_dev, int tile_size, const uint32_t *cuts, int n_cuts,
+                               float *rgba /* n_cuts*W*H*4 */, float *depth /* n_cuts*W*H or NULL */, rt_stats *st);
 
 /* ---- progressive display -------------------------------------------------
  * Tile order <- Adding_Materials::OnUpdate  In-One-Weekend/03_Shadows_and_Materials/materials.cpp:84-152:

@@ -231,7 +231,12 @@ int rt_debug_pixels_kernel(int which, int info[4]);
  * staged in LDS, 3 the one that reads nodes from global memory (also the linear loop's).  RT_E_ARG for
  * any other `which`.  The cap counts 256-lane blocks of the kernels that own a lane per path or pixel
  * (INW: the path-query kernel's grid during a pass; IOW-03: k_iow_pass's); rt_debug_pass_max_blocks
- * returns the previous cap. */
+ * returns the previous cap.
+ *
+ * The tile-list instances of these kernels (rt_render_pass_tiles_async) answer to rt_debug_pass_kernel
+ * too: which = 16 is k_pass_rays, 17 k_pass_fold, 18 k_iow_pass with the BVH staged in LDS, 19 the one
+ * that reads nodes from global memory.  (4..7 and 15 stay RT_E_ARG: hosts and tests rely on it.)
+ * rt_debug_pass_max_blocks caps their grids as it caps the rectangle passes'. */
 int rt_debug_pass_kernel(int which, int info[4]);
 int rt_debug_pass_max_blocks(int blocks);
 /* The adaptive-pass kernels (rt_render_pass_pixels_async, rt_pass_select_async) answer to

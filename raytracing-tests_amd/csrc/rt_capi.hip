@@ -362,6 +362,11 @@ rt_options g_opt = default_options();
 
 int rtamd::scene_device(const rt_dev_scene *s) { return s ? s->device : -1; }
 
+int rtamd::scene_pass_check(const rt_dev_scene *s, int spp) {
+    if (!s || s->spp != spp || s->broken) return RT_E_ARG;
+    return s->tex_missing ? RT_E_UNSUPPORTED : RT_OK;
+}
+
 extern "C" {
 
 int rt_abi_version(void) { return RT_ABI_VERSION; }
@@ -1018,6 +1023,39 @@ int rt_render_passes_iow03(const float *types, const float *records, uint32_t n,
     if (p->show_normal) return RT_E_UNSUPPORTED;
     return passes_blocking(cam, p, cuts, n_cuts, rgba, nullptr, state_out, device, st,
                            [&](rt_dev_scene *s) { return make_iow03(s, types, records, n, p->spp); });
+}
+
+// A pass over a packed tile list: rt_render_pass_async's launches on rt_render_tiles_async's frame; the pass
+// kernels' tile-list instances index state and image by slot.
+int rt_render_pass_tiles_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p, const int *d_tiles,
+                               int n_tiles, int tile_size, uint32_t s0, uint32_t ns, rt_pass_state *d_state_packed,
+                               float *d_out_packed, float *d_out_depth_packed, uint64_t *d_counters, void *stream) {
+    if (!s || !cam || !params_ok(p) || !d_state_packed || p->spp != s->spp || s0 >= uint32_t(p->spp) || s->broken)
+        return RT_E_ARG;
+    if (!d_tiles || n_tiles <= 0 || tile_size <= 0 || tile_size % 16 != 0) return RT_E_ARG;
+    if (uint64_t(n_tiles) * uint64_t(tile_size) * uint64_t(tile_size) > (uint64_t(1) << 31)) return RT_E_ARG;
+    if (s->tex_missing) return RT_E_UNSUPPORTED;  // a textured object and no texture bound (rt_dev_scene_inw_update_device)
+    if (p->show_normal) return RT_E_UNSUPPORTED;  // one normal per sample, no fold state
+    if (ns == 0) return RT_OK;
+    const uint32_t s1 = uint32_t(std::min<uint64_t>(uint64_t(s0) + ns, pass_stop(s)));
+    rt_params whole = *p;
+    whole.tile_x0 = whole.tile_y0 = whole.tile_w = whole.tile_h = 0;  // the list says which pixels
+    rtk::Frame f = make_pass_frame(s, cam, &whole, d_out_packed, d_out_depth_packed, d_counters);
+    f.tiles = d_tiles; f.n_tiles = n_tiles; f.tile_size = tile_size;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    float4 *state = reinterpret_cast<float4 *>(d_state_packed);
+    if (s->kind == 3) {
+        unsigned *queue = s->counter.as<unsigned>() + 192;  // the passes' own: calls on one scene do not overlap
+        const hipError_t e = rtk::launch_iow_pass(f, iow_view(*s), s0, s1, state, queue, s->cus, st);
+        return e == hipSuccess ? RT_OK : launch_failed(e);
+    }
+    return pass_inw_chunks(s, cam, p, rtk::units_of(f), s1 - s0, 0, d_counters, st,
+        [&](const rtk::InwScene &sc, uint32_t c0, uint32_t nsc, float4 *rays) {
+            return rtk::launch_pass_rays(f, sc, s0 + c0, nsc, rays, st);
+        },
+        [&](uint32_t c0, uint32_t nsc, bool last, const float4 *out) {
+            return rtk::launch_pass_fold(f, s0 + c0, nsc, last ? s1 : 0u, out, state, st);
+        });
 }
 
 // ------------------------------------------------------------------------ adaptive sample passes

@@ -533,8 +533,9 @@ int rt_debug_pixels_kernel(int which, int info[4]) {
 }
 
 int rt_debug_pass_kernel(int which, int info[4]) {
-    if (!info || which < 0 || (which > 3 && which < 8) || which > 14) return RT_E_ARG;
-    if (which >= 8) HIP_OK(rtk::adaptive_kernel_info(which - 8, info));  // rt_adaptive.hip's
+    if (!info || which < 0 || (which > 3 && which < 8) || which == 15 || which > 19) return RT_E_ARG;
+    if (which >= 16) HIP_OK(rtk::pass_kernel_info(which - 12, info));  // the tile-list instances
+    else if (which >= 8) HIP_OK(rtk::adaptive_kernel_info(which - 8, info));  // rt_adaptive.hip's
     else HIP_OK(rtk::pass_kernel_info(which, info));
     return RT_OK;
 }

@@ -199,5 +199,10 @@ std::vector<std::pair<int, int>> tile_deal(int W, int H, int T, int n_dev);
 
 // the device a device scene was built on (rt_capi.hip; the multi-GPU group checks its scene list)
 int scene_device(const struct rt_dev_scene *s);
+// what a progressive pass of `spp` samples a pixel would answer for the scene before it touches a device
+// (rt_capi.hip; the group checks every scene of a pass before it changes anything): RT_E_ARG for another
+// spp or a scene a failed update left broken, RT_E_UNSUPPORTED for one an update left without its
+// textures, else RT_OK
+int scene_pass_check(const struct rt_dev_scene *s, int spp);
 
 }  // namespace rtamd

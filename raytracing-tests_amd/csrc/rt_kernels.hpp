@@ -525,7 +525,8 @@ hipError_t launch_pass_rays(const Frame &f, const InwScene &sc, uint32_t s0, uin
 hipError_t launch_pass_fold(const Frame &f, uint32_t s0, uint32_t ns, uint32_t k, const float4 *out, float4 *state,
                             hipStream_t s);
 // {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of k_pass_rays (which = 0), k_pass_fold
-// (1) and k_iow_pass (2 nodes staged in LDS, 3 not)
+// (1) and k_iow_pass (2 nodes staged in LDS, 3 not); 4..7: the same four for a packed tile list.  The
+// three launches above pick the tile-list instance when f.tiles is set (units, state and image by slot).
 hipError_t pass_kernel_info(int which, int info[4]);
 int pass_max_blocks_now();        // the cap rt_debug_pass_max_blocks set (0 = none)
 int pass_max_blocks(int blocks);  // rt_debug_pass_max_blocks: cap the grid (0 = off); the previous cap

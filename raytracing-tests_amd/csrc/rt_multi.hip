@@ -8,6 +8,9 @@
 // single-device dispatch of RT_Base<>::OnUpdateBase (In-Next-Week/base.h:148-173) for a C++ host.
 // bench.py's one-process-per-GPU torchrun path (the driver's scaling run) deals the same tiles
 // (rt_tile_deal == bench.deal_order) and gathers them with torch.distributed on RCCL.
+// Progressive frames (rt_render_pass_multi_async): every device keeps the fold state of its share's slots
+// and continues it with rt_render_pass_tiles_async; a pass that is asked for an image ends in the same
+// exchange and unpack, one that is not sends its counters alone.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -112,6 +115,7 @@ struct rt_group {
     std::vector<hipStream_t> st;  // st[0] unused: device 0 works on the caller's stream
     struct Share {                // one device's share of the frame
         Buf tiles, packed, depth, counters;
+        Buf state;  // the fold state of the share's slots (rt_pass_state, 32 B each): it never leaves its device
         int n_tiles = 0;
     };
     std::vector<std::unique_ptr<Share>> share;
@@ -119,6 +123,7 @@ struct rt_group {
     // the deal the buffers hold (re-uploaded when the frame or tile size changes)
     int W = 0, H = 0, T = 0;
     std::vector<uint32_t> off;  // device r's first tile in the gathered order
+    uint32_t samples = 0;       // rt_render_pass_multi_async: the samples the states hold for this deal
     ~rt_group() {
         share.clear();
         for (ncclComm_t c : comm)
@@ -139,6 +144,7 @@ namespace {
 // API is asynchronous, and a null-stream copy does not wait for non-blocking streams
 int set_deal(rt_group *g, int W, int H, int T, hipStream_t s0) {
     if (g->W == W && g->H == H && g->T == T) return RT_OK;
+    g->samples = 0;  // the states of another deal are no one's
     for (int r = 0; r < g->n; r++) {
         MULTI_HIP(hipSetDevice(g->dev[size_t(r)]));
         MULTI_HIP(hipStreamSynchronize(r == 0 ? s0 : g->st[size_t(r)]));
@@ -164,6 +170,7 @@ int set_deal(rt_group *g, int W, int H, int T, hipStream_t s0) {
         MULTI_HIP(S.packed.ensure(nt * area * 4 * sizeof(float), g->dev[size_t(r)]));
         MULTI_HIP(S.depth.ensure(nt * area * sizeof(float), g->dev[size_t(r)]));
         MULTI_HIP(S.counters.ensure(6 * sizeof(unsigned long long), g->dev[size_t(r)]));
+        MULTI_HIP(S.state.ensure(nt * area * sizeof(rt_pass_state), g->dev[size_t(r)]));
         if (S.n_tiles)
             MULTI_HIP(hipMemcpy(S.tiles.p, lists[size_t(r)].data(), size_t(S.n_tiles) * 2 * sizeof(int),
                                 hipMemcpyHostToDevice));
@@ -176,6 +183,121 @@ int set_deal(rt_group *g, int W, int H, int T, hipStream_t s0) {
     MULTI_HIP(g->recv_ctr.ensure(size_t(g->n) * 6 * sizeof(unsigned long long), g->dev[0]));
     MULTI_HIP(hipMemcpy(g->recv_tiles.p, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
     g->W = W; g->H = H; g->T = T;
+    return RT_OK;
+}
+
+// The one exchange step: every device's packed tiles (with `image`), depth (with d_depth) and counters to
+// device 0 (device 0 sends to itself too, so one code path serves every group size), where one kernel
+// unpacks the tiles into the W x H image and one adds the counters up.  An error inside the group still
+// ends it, so later RCCL calls of this thread are not left inside an open group.
+int gather(rt_group *g, const rt_params *p, int tile_size, bool image, float *d_rgba, float *d_depth,
+           uint64_t *d_counters, hipStream_t s0) {
+    auto stream_of = [&](int r) { return r == 0 ? s0 : g->st[size_t(r)]; };
+    const size_t area = size_t(tile_size) * size_t(tile_size);
+    MULTI_NCCL(ncclGroupStart());
+    ncclResult_t nr = ncclSuccess;
+    auto call = [&](ncclResult_t r_) { if (nr == ncclSuccess) nr = r_; };
+    for (int r = 0; r < g->n && nr == ncclSuccess; r++) {
+        auto &S = *g->share[size_t(r)];
+        if (S.n_tiles && image) {
+            call(ncclSend(S.packed.p, size_t(S.n_tiles) * area * 4, ncclFloat32, 0, g->comm[size_t(r)], stream_of(r)));
+            if (d_depth)
+                call(ncclSend(S.depth.p, size_t(S.n_tiles) * area, ncclFloat32, 0, g->comm[size_t(r)], stream_of(r)));
+        }
+        call(ncclSend(S.counters.p, 6, ncclUint64, 0, g->comm[size_t(r)], stream_of(r)));
+    }
+    for (int r = 0; r < g->n && nr == ncclSuccess; r++) {
+        auto &S = *g->share[size_t(r)];
+        const size_t o = g->off[size_t(r)];
+        if (S.n_tiles && image) {
+            call(ncclRecv(g->recv.as<float>() + o * area * 4, size_t(S.n_tiles) * area * 4, ncclFloat32, r, g->comm[0],
+                          s0));
+            if (d_depth)
+                call(ncclRecv(g->recv_depth.as<float>() + o * area, size_t(S.n_tiles) * area, ncclFloat32, r,
+                              g->comm[0], s0));
+        }
+        call(ncclRecv(g->recv_ctr.as<unsigned long long>() + size_t(r) * 6, 6, ncclUint64, r, g->comm[0], s0));
+    }
+    const ncclResult_t ne = ncclGroupEnd();
+    MULTI_NCCL(nr);
+    MULTI_NCCL(ne);
+    // device 0 assembles the frame
+    MULTI_HIP(hipSetDevice(g->dev[0]));
+    const uint32_t n_px = uint32_t(size_t(g->off[size_t(g->n)]) * area);
+    if (n_px && image)
+        hipLaunchKernelGGL(k_unpack_tiles, dim3((n_px + 255u) / 256u), dim3(256), 0, s0, g->recv.as<float4>(),
+                           g->recv_depth.as<float>(), g->recv_tiles.as<int2>(), n_px, tile_size, p->width, p->height,
+                           reinterpret_cast<float4 *>(d_rgba), d_depth);
+    if (d_counters)
+        hipLaunchKernelGGL(k_sum_counters, dim3(1), dim3(64), 0, s0, g->recv_ctr.as<unsigned long long>(), g->n,
+                           reinterpret_cast<unsigned long long *>(d_counters));
+    MULTI_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+// every scene must live on its group device (its buffers are that device's; a scene of another
+// device would launch there with this device's stream)
+bool scenes_ok(const rt_group *g, rt_dev_scene *const *scenes) {
+    for (int r = 0; r < g->n; r++)
+        if (!scenes[r] || rtamd::scene_device(scenes[r]) != g->dev[size_t(r)]) return false;
+    return true;
+}
+
+// The blocking group calls: the scene replicated on every device, a group for the call, n_img images (and
+// depths, when asked) up to device 0 so that pixels nothing writes keep the caller's bytes, run(group,
+// scenes, d_rgba, d_depth, d_ctr) timed on device 0's null stream, the images and the counters back.
+template <class Run>
+int inw_multi_blocking(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                       uint32_t n_lights, const rt_params *p, const int *devices, int n_dev, size_t n_img, float *rgba,
+                       float *depth, rt_stats *st, Run &&run) {
+    DeviceGuard guard;
+    struct SceneDel { void operator()(rt_dev_scene *s) const { rt_dev_scene_free(s); } };
+    struct GroupDel { void operator()(rt_group *g) const { rt_group_free(g); } };
+    std::vector<std::unique_ptr<rt_dev_scene, SceneDel>> own;
+    std::vector<rt_dev_scene *> scenes;
+    for (int r = 0; r < n_dev; r++) {  // the scene replicated on every device (< 2 MB at C3)
+        rt_dev_scene *s = rt_dev_scene_inw(geom, n, layout, nodes, lights, n_lights, p->spp, devices[r]);
+        if (!s) return RT_E_NODEVICE;
+        own.emplace_back(s);
+        scenes.push_back(s);
+    }
+    std::unique_ptr<rt_group, GroupDel> g(rt_group_create(devices, n_dev));
+    if (!g) return RT_E_NODEVICE;
+    MULTI_HIP(hipSetDevice(devices[0]));
+    const size_t npx = size_t(p->width) * size_t(p->height) * n_img;
+    Buf d_rgba, d_depth, d_ctr;
+    MULTI_HIP(d_rgba.ensure(npx * 16, devices[0]));
+    MULTI_HIP(hipMemcpy(d_rgba.p, rgba, npx * 16, hipMemcpyHostToDevice));
+    if (depth) {
+        MULTI_HIP(d_depth.ensure(npx * 4, devices[0]));
+        MULTI_HIP(hipMemcpy(d_depth.p, depth, npx * 4, hipMemcpyHostToDevice));
+    }
+    MULTI_HIP(d_ctr.ensure(6 * sizeof(unsigned long long), devices[0]));
+    MULTI_HIP(hipMemset(d_ctr.p, 0, 6 * sizeof(unsigned long long)));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    MULTI_HIP(hipEventCreate(&e0));
+    MULTI_HIP(hipEventCreate(&e1));
+    MULTI_HIP(hipEventRecord(e0, nullptr));
+    int rc = run(g.get(), scenes.data(), d_rgba.as<float>(), depth ? d_depth.as<float>() : nullptr,
+                 d_ctr.as<uint64_t>());
+    (void)hipSetDevice(devices[0]);
+    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc != RT_OK) return rc;
+    MULTI_HIP(hipDeviceSynchronize());
+    MULTI_HIP(hipMemcpy(rgba, d_rgba.p, npx * 16, hipMemcpyDeviceToHost));
+    if (depth) MULTI_HIP(hipMemcpy(depth, d_depth.p, npx * 4, hipMemcpyDeviceToHost));
+    if (st) {
+        unsigned long long c[6];
+        MULTI_HIP(hipMemcpy(c, d_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
+        st->segments = c[0]; st->node_visits = c[1]; st->prim_tests = c[2];
+        st->shadow_queries = c[3]; st->stack_drops = c[4]; st->nan_drops = c[5];
+        st->ms = ms;
+    }
     return RT_OK;
 }
 
@@ -246,10 +368,7 @@ int rt_render_multi_async(rt_group *g, rt_dev_scene *const *scenes, const rt_cam
     if (!g || !scenes || !cam || !p || !d_rgba || p->width <= 0 || p->height <= 0 || tile_size <= 0 ||
         tile_size % 16 != 0)
         return RT_E_ARG;
-    // every scene must live on its group device (its buffers are that device's; a scene of another
-    // device would launch there with this device's stream)
-    for (int r = 0; r < g->n; r++)
-        if (!scenes[r] || rtamd::scene_device(scenes[r]) != g->dev[size_t(r)]) return RT_E_ARG;
+    if (!scenes_ok(g, scenes)) return RT_E_ARG;
     DeviceGuard guard;
     const hipStream_t s0 = static_cast<hipStream_t>(stream);
     if (int rc = set_deal(g, p->width, p->height, tile_size, s0); rc != RT_OK) {
@@ -257,7 +376,6 @@ int rt_render_multi_async(rt_group *g, rt_dev_scene *const *scenes, const rt_cam
         return rc;
     }
     auto stream_of = [&](int r) { return r == 0 ? s0 : g->st[size_t(r)]; };
-    const size_t area = size_t(tile_size) * size_t(tile_size);
     rt_params q = *p;
     q.tile_x0 = q.tile_y0 = q.tile_w = q.tile_h = 0;  // the whole frame
     // every device renders its share on its own stream
@@ -271,48 +389,53 @@ int rt_render_multi_async(rt_group *g, rt_dev_scene *const *scenes, const rt_cam
                                              S.counters.as<uint64_t>(), stream_of(r));
         if (rc != RT_OK) return rc;
     }
-    // the one exchange step: every device's packed tiles, depth and counters to device 0
-    // (device 0 sends to itself too, so one code path serves every group size).  An error inside
-    // the group still ends it, so later RCCL calls of this thread are not left inside an open group
-    MULTI_NCCL(ncclGroupStart());
-    ncclResult_t nr = ncclSuccess;
-    auto call = [&](ncclResult_t r_) { if (nr == ncclSuccess) nr = r_; };
-    for (int r = 0; r < g->n && nr == ncclSuccess; r++) {
-        auto &S = *g->share[size_t(r)];
-        if (S.n_tiles) {
-            call(ncclSend(S.packed.p, size_t(S.n_tiles) * area * 4, ncclFloat32, 0, g->comm[size_t(r)], stream_of(r)));
-            if (d_depth)
-                call(ncclSend(S.depth.p, size_t(S.n_tiles) * area, ncclFloat32, 0, g->comm[size_t(r)], stream_of(r)));
-        }
-        call(ncclSend(S.counters.p, 6, ncclUint64, 0, g->comm[size_t(r)], stream_of(r)));
+    return gather(g, p, tile_size, true, d_rgba, d_depth, d_counters, s0);
+}
+
+int rt_render_pass_multi_async(rt_group *g, rt_dev_scene *const *scenes, const rt_camera *cam, const rt_params *p,
+                               int tile_size, uint32_t s0, uint32_t ns, float *d_rgba, float *d_depth,
+                               uint64_t *d_counters, void *stream) {
+    if (!g || !scenes || !cam || !p || p->width <= 0 || p->height <= 0 || p->spp < 1 || p->max_bounces < 0 ||
+        tile_size <= 0 || tile_size % 16 != 0 || s0 >= uint32_t(p->spp))
+        return RT_E_ARG;
+    if (!scenes_ok(g, scenes)) return RT_E_ARG;
+    // everything a device's pass could refuse is asked of every scene first, so that a refused call leaves
+    // the deal, the states and their count as they were: argument errors of any scene before RT_E_UNSUPPORTED
+    bool unsupported = p->show_normal != 0;
+    for (int r = 0; r < g->n; r++) {
+        const int rc = rtamd::scene_pass_check(scenes[r], p->spp);
+        if (rc == RT_E_ARG) return RT_E_ARG;
+        unsupported |= rc != RT_OK;
     }
-    for (int r = 0; r < g->n && nr == ncclSuccess; r++) {
-        auto &S = *g->share[size_t(r)];
-        const size_t o = g->off[size_t(r)];
-        if (S.n_tiles) {
-            call(ncclRecv(g->recv.as<float>() + o * area * 4, size_t(S.n_tiles) * area * 4, ncclFloat32, r, g->comm[0],
-                          s0));
-            if (d_depth)
-                call(ncclRecv(g->recv_depth.as<float>() + o * area, size_t(S.n_tiles) * area, ncclFloat32, r,
-                              g->comm[0], s0));
-        }
-        call(ncclRecv(g->recv_ctr.as<unsigned long long>() + size_t(r) * 6, 6, ncclUint64, r, g->comm[0], s0));
+    // the samples the states hold: none when this call changes the deal
+    const uint32_t held = (g->W == p->width && g->H == p->height && g->T == tile_size) ? g->samples : 0u;
+    if (s0 != 0 && s0 != held) return RT_E_ARG;
+    if (unsupported) return RT_E_UNSUPPORTED;
+    if (ns == 0) return RT_OK;
+    DeviceGuard guard;
+    const hipStream_t st0 = static_cast<hipStream_t>(stream);
+    if (int rc = set_deal(g, p->width, p->height, tile_size, st0); rc != RT_OK) {
+        g->W = 0;  // rebuild the deal next time
+        return rc;
     }
-    const ncclResult_t ne = ncclGroupEnd();
-    MULTI_NCCL(nr);
-    MULTI_NCCL(ne);
-    // device 0 assembles the frame
-    MULTI_HIP(hipSetDevice(g->dev[0]));
-    const uint32_t n_px = uint32_t(size_t(g->off[size_t(g->n)]) * area);
-    if (n_px)
-        hipLaunchKernelGGL(k_unpack_tiles, dim3((n_px + 255u) / 256u), dim3(256), 0, s0, g->recv.as<float4>(),
-                           g->recv_depth.as<float>(), g->recv_tiles.as<int2>(), n_px, tile_size, p->width, p->height,
-                           reinterpret_cast<float4 *>(d_rgba), d_depth);
-    if (d_counters)
-        hipLaunchKernelGGL(k_sum_counters, dim3(1), dim3(64), 0, s0, g->recv_ctr.as<unsigned long long>(), g->n,
-                           reinterpret_cast<unsigned long long *>(d_counters));
-    MULTI_HIP(hipGetLastError());
-    return RT_OK;
+    auto stream_of = [&](int r) { return r == 0 ? st0 : g->st[size_t(r)]; };
+    const bool image = d_rgba != nullptr, want_depth = image && d_depth != nullptr;
+    g->samples = 0;  // until every device has taken the pass: a failed one leaves states of no count
+    // every device continues the states of its share on its own stream
+    for (int r = 0; r < g->n; r++) {
+        auto &S = *g->share[size_t(r)];
+        MULTI_HIP(hipSetDevice(g->dev[size_t(r)]));
+        MULTI_HIP(hipMemsetAsync(S.counters.p, 0, 6 * sizeof(unsigned long long), stream_of(r)));
+        if (S.n_tiles == 0) continue;
+        const int rc = rt_render_pass_tiles_async(scenes[r], cam, p, S.tiles.as<int>(), S.n_tiles, tile_size, s0, ns,
+                                                  S.state.as<rt_pass_state>(), image ? S.packed.as<float>() : nullptr,
+                                                  want_depth ? S.depth.as<float>() : nullptr,
+                                                  S.counters.as<uint64_t>(), stream_of(r));
+        if (rc != RT_OK) return rc;
+    }
+    const int rc = gather(g, p, tile_size, image, d_rgba, want_depth ? d_depth : nullptr, d_counters, st0);
+    if (rc == RT_OK) g->samples = uint32_t(std::min<uint64_t>(uint64_t(s0) + ns, uint64_t(p->spp)));
+    return rc;
 }
 
 int rt_render_inw_multi(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
@@ -321,55 +444,38 @@ int rt_render_inw_multi(const float *geom, uint32_t n, int layout, const float *
     if (!geom || !nodes || n == 0 || !cam || !p || p->width <= 0 || p->height <= 0 || p->spp < 1 || !rgba ||
         !devices || n_dev <= 0 || (layout != 1 && layout != 4))
         return RT_E_ARG;
-    DeviceGuard guard;
-    struct SceneDel { void operator()(rt_dev_scene *s) const { rt_dev_scene_free(s); } };
-    struct GroupDel { void operator()(rt_group *g) const { rt_group_free(g); } };
-    std::vector<std::unique_ptr<rt_dev_scene, SceneDel>> own;
-    std::vector<rt_dev_scene *> scenes;
-    for (int r = 0; r < n_dev; r++) {  // the scene replicated on every device (< 2 MB at C3)
-        rt_dev_scene *s = rt_dev_scene_inw(geom, n, layout, nodes, lights, n_lights, p->spp, devices[r]);
-        if (!s) return RT_E_NODEVICE;
-        own.emplace_back(s);
-        scenes.push_back(s);
-    }
-    std::unique_ptr<rt_group, GroupDel> g(rt_group_create(devices, n_dev));
-    if (!g) return RT_E_NODEVICE;
-    MULTI_HIP(hipSetDevice(devices[0]));
+    return inw_multi_blocking(geom, n, layout, nodes, lights, n_lights, p, devices, n_dev, 1, rgba, depth, st,
+        [&](rt_group *g, rt_dev_scene *const *scenes, float *d_rgba, float *d_depth, uint64_t *d_ctr) {
+            return rt_render_multi_async(g, scenes, cam, p, tile_size, d_rgba, d_depth, d_ctr, nullptr);
+        });
+}
+
+int rt_render_passes_inw_multi(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                               uint32_t n_lights, const rt_camera *cam, const rt_params *p, const int *devices,
+                               int n_dev, int tile_size, const uint32_t *cuts, int n_cuts, float *rgba, float *depth,
+                               rt_stats *st) {
+    if (!geom || !nodes || n == 0 || !cam || !p || p->width <= 0 || p->height <= 0 || p->spp < 1 || !rgba ||
+        !devices || n_dev <= 0 || (layout != 1 && layout != 4) || tile_size <= 0 || tile_size % 16 != 0)
+        return RT_E_ARG;
+    if (layout == 4 && n_lights > 0 && !lights) return RT_E_ARG;
+    // rt_render_passes_inw's rule: strictly increasing from cuts[0] > 0 to at most spp
+    if (!cuts || n_cuts < 1 || cuts[0] == 0 || cuts[n_cuts - 1] > uint32_t(p->spp)) return RT_E_ARG;
+    for (int i = 1; i < n_cuts; i++)
+        if (cuts[i] <= cuts[i - 1]) return RT_E_ARG;
+    if (p->show_normal) return RT_E_UNSUPPORTED;
     const size_t npx = size_t(p->width) * size_t(p->height);
-    Buf d_rgba, d_depth, d_ctr;
-    MULTI_HIP(d_rgba.ensure(npx * 16, devices[0]));
-    MULTI_HIP(hipMemcpy(d_rgba.p, rgba, npx * 16, hipMemcpyHostToDevice));
-    if (depth) {
-        MULTI_HIP(d_depth.ensure(npx * 4, devices[0]));
-        MULTI_HIP(hipMemcpy(d_depth.p, depth, npx * 4, hipMemcpyHostToDevice));
-    }
-    MULTI_HIP(d_ctr.ensure(6 * sizeof(unsigned long long), devices[0]));
-    MULTI_HIP(hipMemset(d_ctr.p, 0, 6 * sizeof(unsigned long long)));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    MULTI_HIP(hipEventCreate(&e0));
-    MULTI_HIP(hipEventCreate(&e1));
-    MULTI_HIP(hipEventRecord(e0, nullptr));
-    int rc = rt_render_multi_async(g.get(), scenes.data(), cam, p, tile_size, d_rgba.as<float>(),
-                                   depth ? d_depth.as<float>() : nullptr, d_ctr.as<uint64_t>(), nullptr);
-    (void)hipSetDevice(devices[0]);
-    (void)hipEventRecord(e1, nullptr);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc != RT_OK) return rc;
-    MULTI_HIP(hipDeviceSynchronize());
-    MULTI_HIP(hipMemcpy(rgba, d_rgba.p, npx * 16, hipMemcpyDeviceToHost));
-    if (depth) MULTI_HIP(hipMemcpy(depth, d_depth.p, npx * 4, hipMemcpyDeviceToHost));
-    if (st) {
-        unsigned long long c[6];
-        MULTI_HIP(hipMemcpy(c, d_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
-        st->segments = c[0]; st->node_visits = c[1]; st->prim_tests = c[2];
-        st->shadow_queries = c[3]; st->stack_drops = c[4]; st->nan_drops = c[5];
-        st->ms = ms;
-    }
-    return RT_OK;
+    return inw_multi_blocking(geom, n, layout, nodes, lights, n_lights, p, devices, n_dev, size_t(n_cuts), rgba, depth, st,
+        [&](rt_group *g, rt_dev_scene *const *scenes, float *d_rgba, float *d_depth, uint64_t *d_ctr) {
+            uint32_t s0 = 0;
+            for (int i = 0; i < n_cuts; i++) {  // pass i into image i
+                const int rc = rt_render_pass_multi_async(g, scenes, cam, p, tile_size, s0, cuts[i] - s0,
+                                                          d_rgba + size_t(i) * npx * 4,
+                                                          d_depth ? d_depth + size_t(i) * npx : nullptr, d_ctr, nullptr);
+                if (rc != RT_OK) return rc;
+                s0 = cuts[i];
+            }
+            return int(RT_OK);
+        });
 }
 
 }  // extern "C"

@@ -27,6 +27,24 @@ __device__ __forceinline__ void pass_frame(Frame &F, const Frame &in) {
     F.dir[0] = in.dir[0]; F.dir[1] = in.dir[1]; F.dir[2] = in.dir[2];
     F.aperture = in.aperture; F.focus = in.focus; F.screen_dist = in.screen_dist;
 }
+// The same with the packed tile list kept: the frame of the tile-list instances (rt_render_pass_tiles_async).
+// The rectangle instances never call it, so they keep `tiles` a constant 0 and lose the list's code.
+__device__ __forceinline__ void pass_frame_tiles(Frame &F, const Frame &in) {
+    pass_frame(F, in);
+    F.tiles = in.tiles; F.n_tiles = in.n_tiles; F.tile_size = in.tile_size;
+}
+template <bool TL>
+__device__ __forceinline__ void pass_frame_of(Frame &F, const Frame &in) {
+    if (TL) pass_frame_tiles(F, in);
+    else pass_frame(F, in);
+}
+// Unit u's pixel: unit_pixel, which a tile-list instance reads with the list known to be there (units
+// tile-major, 8x8 blocks inside a tile; p.out = the slot tile * T * T + iy * T + ix).
+template <bool TL>
+__device__ __forceinline__ UnitPix pass_unit_pixel(const Frame &F, uint32_t u) {
+    if (TL) __builtin_assume(F.tiles != nullptr);
+    return unit_pixel(F, u);
+}
 // ... and what a segment reads (k_inw_paths' and k_iow_paths' frames)
 __device__ __forceinline__ void pass_seg_frame(Frame &F, const Frame &in) {
     F.max_bounces = in.max_bounces;
@@ -47,6 +65,12 @@ __device__ __forceinline__ void pass_write_image(const Frame &F, size_t o, f3 ac
         reinterpret_cast<float4 *>(F.out_rgba)[o] = make_float4(v.x, v.y, v.z, 1.0f);
     }
     if (F.out_depth) F.out_depth[o] = depth;
+}
+
+// A packed slot outside the image: (0, 0, 0, 0) and the depth 0, as rt_render_tiles_async writes it.
+__device__ __forceinline__ void pass_write_outside(const Frame &F, size_t o) {
+    if (F.out_rgba) reinterpret_cast<float4 *>(F.out_rgba)[o] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (F.out_depth) F.out_depth[o] = 0.0f;
 }
 
 // ------------------------------------------------------------------------------------------ INW

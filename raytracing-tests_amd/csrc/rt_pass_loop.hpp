@@ -16,11 +16,18 @@ template <bool LN> constexpr int kPassIowWaves = LN ? 2 : 3;
 
 // Every unit of the frame's rectangle (unit_pixel) renders samples [s0, s1); the image is acc * inv_k.
 // All its answers are wave-uniform: none reads a lane's own sample or last sample.
-struct UniformPass {
+// TL: the units are those of the frame's packed tile list (rt_render_pass_tiles_async) and the state and
+// image are indexed by slot; a slot outside the image gets the zero image the tile renders write.
+template <bool TL>
+struct UniformPassOf {
     static constexpr bool kEven = false;
     uint32_t s0, s1;
     float inv_k;
-    __device__ __forceinline__ UnitPix pixel(const Frame &F, uint32_t u) const { return unit_pixel(F, u); }
+    __device__ __forceinline__ void frame(Frame &F, const Frame &in) const { pass_frame_of<TL>(F, in); }
+    __device__ __forceinline__ UnitPix pixel(const Frame &F, uint32_t u) const { return pass_unit_pixel<TL>(F, u); }
+    __device__ __forceinline__ void outside(const Frame &F, const UnitPix &p) const {
+        if (TL) pass_write_outside(F, p.out);
+    }
     __device__ __forceinline__ uint32_t first(size_t, f3 &) const { return s0; }
     __device__ __forceinline__ bool fresh(uint32_t) const { return s0 == 0; }
     __device__ __forceinline__ bool left(uint32_t) const { return s0 < s1; }
@@ -29,6 +36,7 @@ struct UniformPass {
     __device__ __forceinline__ float inv(uint32_t) const { return inv_k; }
     __device__ __forceinline__ void keep(size_t, f3, uint32_t) const {}
 };
+using UniformPass = UniformPassOf<false>;
 
 // Unit u is list entry u; its pixel renders samples [count, min(count + ns, stop)), count = its aux's
 // (aux: even.xyz, the count's bits), folds `even` and leaves even and the new count behind; the image is
@@ -38,6 +46,8 @@ struct ListPass {
     const int2 *__restrict__ pixels;
     float4 *__restrict__ aux;
     uint32_t stop, ns;
+    __device__ __forceinline__ void frame(Frame &F, const Frame &in) const { pass_frame(F, in); }
+    __device__ __forceinline__ void outside(const Frame &, const UnitPix &) const {}
     __device__ __forceinline__ UnitPix pixel(const Frame &F, uint32_t u) const {
         const int2 p = pixels[u];
         UnitPix q;
@@ -69,7 +79,7 @@ __device__ __forceinline__ void iow_pass_loop(const Frame &Fin, const IowScene &
                                               float4 *__restrict__ state, unsigned *queue, uint32_t rounds,
                                               uint32_t n_units) {
     Frame F{}, Fs{};
-    pass_frame(F, Fin);
+    src.frame(F, Fin);
     pass_seg_frame(Fs, Fin);
     using Cfg = IowCfg<false, 1, LN>;
     using Stack = IowStack<false>;
@@ -129,6 +139,8 @@ __device__ __forceinline__ void iow_pass_loop(const Frame &Fin, const IowScene &
                     } else {  // nothing left to render: the image from the state as it is
                         pass_write_image(F, out, fc, src.inv(s), 0.0f);
                     }
+                } else {
+                    src.outside(F, p);  // a tile list's slot outside the image: the zero image
                 }
             }
             next += want < avail ? want : avail;

@@ -267,6 +267,15 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
                                       C.POINTER(RtParams), _IP, C.c_int, C.c_int, _FP, _FP, C.POINTER(RtStats)]),
+    "rt_render_pass_tiles_async": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_void_p,
+                                             C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_pass_multi_async": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams),
+                                             C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "rt_render_passes_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
+                                             C.POINTER(RtParams), _IP, C.c_int, C.c_int, _U32P, C.c_int, _FP, _FP,
+                                             C.POINTER(RtStats)]),
 }
 
 _lib = None
@@ -1000,9 +1009,14 @@ def render_passes(sc: Scene, cuts, want_state: bool = False, params: RtParams | 
 PASS_KERNELS = ("k_pass_rays (INW)", "k_pass_fold (INW)", "k_iow_pass LDS nodes", "k_iow_pass global nodes")
 
 
+# rt_debug_pass_kernel's `which` of the tile-list instances (rt_render_pass_tiles_async)
+PASS_TILE_KERNELS = {16: "k_pass_rays tile list (INW)", 17: "k_pass_fold tile list (INW)",
+                     18: "k_iow_pass tile list, LDS nodes", 19: "k_iow_pass tile list, global nodes"}
+
+
 def pass_kernel_info(which: int) -> dict:
     """rt_debug_pass_kernel: registers, scratch, LDS and resident blocks per CU of PASS_KERNELS[which]
-    (which = 0..3) or ADAPTIVE_KERNELS[which] (8..14)."""
+    (which = 0..3), ADAPTIVE_KERNELS[which] (8..14) or PASS_TILE_KERNELS[which] (16..19)."""
     info = (C.c_int * 4)()
     check(load().rt_debug_pass_kernel(int(which), info), "rt_debug_pass_kernel")
     return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
@@ -1057,6 +1071,34 @@ def pass_pixels(handle, camera: RtCamera, params: RtParams, d_pixels, n_pixels: 
     return load().rt_render_pass_pixels_async(handle, C.byref(camera), C.byref(params), _dptr(d_pixels), n_pixels, ns,
                                               _dptr(d_state), _dptr(d_aux), _dptr(d_rgba), _dptr(d_depth),
                                               _dptr(d_counters), stream)
+
+
+def render_pass_tiles(handle, camera: RtCamera, params: RtParams, d_tiles, n_tiles: int, tile_size: int, s0: int,
+                      ns: int, d_state, d_out=None, d_depth=None, d_counters=None, stream=None) -> int:
+    """rt_render_pass_tiles_async on device buffers (pointers or torch tensors); returns the status."""
+    return load().rt_render_pass_tiles_async(handle, C.byref(camera), C.byref(params), _dptr(d_tiles), n_tiles,
+                                             tile_size, s0, ns, _dptr(d_state), _dptr(d_out), _dptr(d_depth),
+                                             _dptr(d_counters), stream)
+
+
+def render_passes_multi(sc: Scene, devices, cuts, tile: int = 16, rgba=None, depth=None) -> dict:
+    """rt_render_passes_inw_multi: the blocking progressive passes of the INW frame (sc.camera, sc.params) on
+    the device group `devices`.  Returns {"rgba": (n_cuts, H, W, 4), "depth": (n_cuts, H, W), "stats": dict};
+    rgba and depth: arrays of those shapes to start from, default zeros."""
+    p = sc.params
+    cuts = np.ascontiguousarray(cuts, np.uint32).reshape(-1)
+    n, H, W = len(cuts), p.height, p.width
+    rgba = np.zeros((n, H, W, 4), np.float32) if rgba is None else np.ascontiguousarray(rgba, np.float32)
+    depth = np.zeros((n, H, W), np.float32) if depth is None else np.ascontiguousarray(depth, np.float32)
+    assert rgba.shape == (n, H, W, 4) and depth.shape == (n, H, W)
+    devs = (C.c_int * len(devices))(*devices)
+    lights = sc.lights if sc.lights is not None and len(sc.lights) else None
+    st = RtStats()
+    check(load().rt_render_passes_inw_multi(fptr(sc.geom), sc.n, sc.layout, fptr(sc.nodes), fptr(lights), sc.n_lights,
+                                            C.byref(sc.camera), C.byref(p), devs, len(devices), tile,
+                                            cuts.ctypes.data_as(_U32P), n, fptr(rgba), fptr(depth), C.byref(st)),
+          "rt_render_passes_inw_multi")
+    return {"rgba": rgba, "depth": depth, "stats": st.as_dict()}
 
 
 def pass_select(handle, params: RtParams, d_state, d_aux, tol: float, min_samples: int, d_list, d_n_active,
