@@ -901,8 +901,8 @@ int rt_render_inw_multi(const float *geom, uint32_t n, int layout, const float *
  * Returns RT_E_ARG, before a device is touched and with the buffers untouched, for the passes'
  * conditions, null d_tiles, n_tiles <= 0, a bad tile_size or n_tiles * T*T > 2^31; then
  * RT_E_UNSUPPORTED for p->show_normal != 0 or a scene an update left without its textures.
- * The adaptive calls (pixel lists: rt_render_pass_pixels_async, rt_pass_select_async) stay uncovered on
- * tile lists and on groups. */
+ * The adaptive calls are served on tile lists and on groups by rt_render_pass_slots_async,
+ * rt_pass_select_tiles_async and rt_render_adaptive_multi_async below. */
 int rt_render_pass_tiles_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p,
                                const int *d_tiles, int n_tiles, int tile_size,
                                uint32_t s0, uint32_t ns,
@@ -940,6 +940,100 @@ int rt_render_passes_inw_multi(const float *geom, uint32_t n, int layout, const 
                                uint32_t n_lights, const rt_camera *cam, const rt_params *p, const int *devices,
                                int n_dev, int tile_size, const uint32_t *cuts, int n_cuts,
                                float *rgba /* n_cuts*W*H*4 */, float *depth /* n_cuts*W*H or NULL */, rt_stats *st);
+
+/* Adaptive sample passes on packed tile lists and on device groups: rt_render_pass_pixels_async and
+ * rt_pass_select_async with everything indexed by slot, so that a host that deals a frame over several
+ * devices stops sampling where the image has settled.  Whether a pixel is active depends only on its own
+ * state and aux, so a partition's adaptive loop gives, bit for bit, the single-device loop's image, depth,
+ * counts and reference counters.
+ *
+ * A list entry on a tile list is a slot, slot = tile * T*T + iy * T + ix as in rt_render_pass_tiles_async;
+ * RT_SLOT_NONE is the padding value.  Tiles, tile_size and the packed buffers are that call's; p->tile_* is
+ * ignored; T need not be a power of two (48 is legal).
+ *
+ * rt_render_pass_slots_async is rt_render_pass_pixels_async over slots.
+ *   - A listed slot is handled when it is below n_tiles * T*T and its pixel (tiles[tile].x * T + ix,
+ *     tiles[tile].y * T + iy) lies inside the image.  With c = d_aux_packed[slot].count it renders samples
+ *     [c, min(c + ns, S)); the state is continued and not read when c == 0, `even` and count are continued
+ *     too; the image acc * RN(1 / c') with alpha 1 and the state's depth (0 on IOW-03) are written to the
+ *     slot.  A listed slot with c >= S renders nothing and has its image rewritten from its state.
+ *   - Any other entry is skipped: RT_SLOT_NONE, an entry past the list's slots, a slot outside the image.
+ *     So a host can launch with the list's full capacity after a select without reading the count back.
+ *   - Unlisted slots keep every byte of state, aux, image and depth.  The zero image of the slots outside
+ *     the image is never written here: it stays the uniform tile pass's and the tile render's business.
+ *   - The list holds no slot twice: the caller's duty, unchecked.
+ * A slot inside the image ends byte-equal to what rt_render_pass_pixels_async leaves for its pixel, given the
+ * same starting count and ns: state, aux, image and depth.  Counters, options, allocation and
+ * synchronisation are the listed passes': [0], [3], [4], [5] (INW) or [0], [4], [5] (IOW-03), summed over a
+ * partition's lists and a frame's rounds, are the single-device loop's; the call never synchronises; an INW
+ * scene grows its pass workspace on the first call of a list size (rt_debug_adaptive_chunk caps the chunks
+ * as it does for pixel lists), IOW-03 allocates nothing.
+ *
+ * rt_pass_select_tiles_async applies rt_pass_select_async's rule (the same operations in the same order,
+ * err = +inf for n < 2, a NaN keeps a slot active) to every slot of the list that lies inside the image.
+ * d_slots[0 .. n_active) receives the active slots in the order of the tile passes' units:
+ * tile-major, 8x8 blocks row-major inside a tile, pixels row-major inside a block.  The following entries are RT_SLOT_NONE,
+ * up to the number of slots inside the image; entries past that keep their bytes.  d_err_packed[slot] gets
+ * the estimate of the slots inside the image, the others keep their bytes.  Three launches, no
+ * synchronisation; the scene's select scratch grows on the first call of a list size.
+ *
+ * Both return RT_E_ARG, before a device is touched and with the buffers untouched, for the conditions of
+ * rt_render_pass_pixels_async and rt_pass_select_async, null d_tiles, n_tiles <= 0, a tile_size that is not a
+ * positive multiple of 16, n_tiles * T*T > 2^31, n_slots > 2^31 or null d_slots with n_slots > 0; then
+ * RT_E_UNSUPPORTED for p->show_normal != 0 or a scene an update left without its textures.
+ * n_slots == 0 or ns == 0 returns RT_OK and launches nothing. */
+#define RT_SLOT_NONE 0xffffffffu
+int rt_render_pass_slots_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p,
+                               const int *d_tiles, int n_tiles, int tile_size,
+                               const uint32_t *d_slots, uint32_t n_slots, uint32_t ns,
+                               rt_pass_state *d_state_packed /* n_tiles*T*T */, rt_pass_aux *d_aux_packed /* same */,
+                               float *d_out_packed /* may be NULL */, float *d_out_depth_packed /* may be NULL */,
+                               uint64_t *d_counters /* may be NULL */, void *stream);
+int rt_pass_select_tiles_async(rt_dev_scene *s, const rt_params *p,
+                               const int *d_tiles, int n_tiles, int tile_size,
+                               const rt_pass_state *d_state_packed, const rt_pass_aux *d_aux_packed,
+                               float tol, uint32_t min_samples,
+                               uint32_t *d_slots /* n_tiles*T*T */, uint32_t *d_n_active,
+                               float *d_err_packed /* may be NULL */, void *stream);
+/* One adaptive round of a group's frame.  The deal, the streams, the scene checks and the device-0 pointers
+ * are rt_render_pass_multi_async's.  Beside the states the group owns, per device, the aux records of its
+ * share, a slot list with its active count, and packed image and depth buffers of the adaptive frame of their
+ * own, so that an rt_render_multi_async frame between two rounds disturbs nothing; they are allocated when a
+ * deal's first adaptive frame begins.
+ * first != 0 begins a frame: every device zeroes its aux and lists every slot of its share that lies inside
+ * the image.  A round runs, on every device and its own stream, rt_render_pass_slots_async (ns samples) over
+ * the current list and rt_pass_select_tiles_async (tol, min_samples) for the next one, and copies the active
+ * count to pinned host memory behind an event.  The grouped send / recv brings the packed image (with d_rgba),
+ * the depth (with d_rgba and d_depth), the counts (with d_count: W*H sample counts) and the counters to device
+ * 0, where the W x H buffers are unpacked.  Pixels that were not listed keep the values of the round they were
+ * last in; nothing depends on slots outside the image.  Image, depth, counts and, summed over the rounds,
+ * the counters [0], [3], [4], [5] are byte-equal to the single-device loop's (rt_render_pass_pixels_async +
+ * rt_pass_select_async) round for round.
+ * THIS CALL BLOCKS in one place: a round with first == 0 waits on the host for the previous round's counts,
+ * launches no pass on a device whose list is empty and sizes each device's launches by its count.
+ * rt_group_adaptive_active waits for the last round's counts too and returns their sum (RT_E_ARG when the
+ * group holds no adaptive frame).
+ * first == 0 is RT_E_ARG with nothing launched when the states of the current deal were not left by an
+ * adaptive round: no frame was begun, the deal changed, or an rt_render_pass_multi_async pass ran since.
+ * Beginning an adaptive frame sets the progressive count to 0, so rt_render_pass_multi_async refuses to
+ * continue into it.  The other argument errors, RT_E_UNSUPPORTED and ns == 0 are rt_render_pass_multi_async's;
+ * every scene is asked before the group is touched.  Not captured into graphs, as the group passes. */
+int rt_render_adaptive_multi_async(rt_group *g, rt_dev_scene *const *scenes, const rt_camera *cam, const rt_params *p,
+                                   int tile_size, int first, uint32_t ns, float tol, uint32_t min_samples,
+                                   float *d_rgba /* may be NULL */, float *d_depth /* may be NULL */,
+                                   uint32_t *d_count /* W*H, may be NULL */, uint64_t *d_counters /* may be NULL */,
+                                   void *stream);
+int rt_group_adaptive_active(rt_group *g, uint32_t *n_active);   /* waits for the last round's counts; their sum */
+/* Blocking form: rt_render_passes_inw_multi's scenes and group, rt_render_adaptive_inw's loop and stopping
+ * rule.  rgba, depth, count and rounds_out are byte-equal to rt_render_adaptive_inw's for the whole frame, as
+ * are the stats segments, shadow_queries, stack_drops and nan_drops.  err, state_out and aux_out are not
+ * offered: fold state does not leave its device.  RT_E_ARG also for batch == 0 or a bad tile_size. */
+int rt_render_adaptive_inw_multi(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                                 uint32_t n_lights, const rt_camera *cam, const rt_params *p,
+                                 const int *devices, int n_dev, int tile_size,
+                                 uint32_t batch, float tol, uint32_t min_samples, uint32_t max_rounds,
+                                 float *rgba, float *depth /* or NULL */, uint32_t *count /* or NULL */,
+                                 uint32_t *rounds_out, rt_stats *st);
 
 /* ---- progressive display -------------------------------------------------
  * Tile order <- Adding_Materials::OnUpdate  In-One-Weekend/03_Shadows_and_Materials/materials.cpp:84-152:

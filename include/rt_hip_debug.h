@@ -246,7 +246,13 @@ int rt_debug_pass_max_blocks(int blocks);
  * kernels existed.)  rt_debug_pass_max_blocks also caps the grids of a listed pass.
  * rt_debug_adaptive_chunk caps the samples of one chunk of an INW listed pass (0 = the default: as many as
  * the workspace rule allows), so that a test can make a small pass run in several chunks; it returns the
- * previous cap. */
+ * previous cap.
+ *
+ * The tile-list instances of the adaptive kernels (rt_render_pass_slots_async, rt_pass_select_tiles_async)
+ * are an adaptive kernel's `which` + 16, as 16..19 are 0..3 + 16: which = 24 is k_adapt_rays, 25 k_adapt_fold,
+ * 26 k_iow_adapt with the BVH staged in LDS, 27 the one that reads nodes from global memory, 28
+ * k_select_count, 30 k_select_scatter.  k_select_scan (13) serves both forms, so 29 is RT_E_ARG, as 20..23
+ * and every value past 30 are.  Both caps apply to a listed pass over slots as to one over pixels. */
 int rt_debug_adaptive_chunk(int samples);
 
 #ifdef __cplusplus

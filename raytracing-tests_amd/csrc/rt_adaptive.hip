@@ -21,6 +21,12 @@
 // Select: a stable partition of the rectangle's units (unit_pixel's order) in three plain launches --
 // per-block counts, an exclusive scan of the block partials in one block, the scatter.  No block waits on
 // another block.
+// Every kernel but the scan has a second instance, TL, for rt_render_pass_slots_async and
+// rt_pass_select_tiles_async: a list entry is a slot of a packed tile list (PassEntry<TL>), state, aux, image,
+// err and answers are indexed by slot, and the select's units are the list's.  The pixel-list instances drop
+// the tile list with pass_frame and keep their code, as rt_passes.hip's rectangle instances do.
+#include <type_traits>
+
 #include "rt_pass_loop.hpp"
 
 namespace rtk {
@@ -28,23 +34,41 @@ namespace rtk {
 // rt_pass_aux as the kernels read it: (even.xyz, count bits)
 __device__ __forceinline__ uint32_t aux_count(const float4 *aux, size_t out) { return __float_as_uint(aux[out].w); }
 
+// A list entry as the INW pair reads it: its pixel, whether it is handled, and (TL) its slot.  The index of
+// its state, aux and image is y * W + x, or the slot on a packed tile list.
+struct Entry { int x, y; bool listed; uint32_t slot; };
+template <bool TL>
+__device__ __forceinline__ Entry entry_of(const Frame &F, PassEntry<TL> e) {
+    if constexpr (TL) {
+        const UnitPix q = slot_pixel(F, e);
+        return Entry{q.x, q.y, q.in_image, e};
+    } else {
+        return Entry{e.x, e.y, listed(F, e), 0u};
+    }
+}
+template <bool TL>
+__device__ __forceinline__ size_t entry_index(const Frame &F, const Entry &p) {
+    return TL ? (size_t)p.slot : (size_t)p.y * F.W + p.x;
+}
+
 // ------------------------------------------------------------------------------------------ INW
 // One lane per record: record k * ns + j is the camera ray of sample count + j of entry k's pixel
 // (pass_ray_record); the sample is the invalid one past `stop` or for an entry outside the image.
 // n = n_pixels * ns <= 2^31.
+template <bool TL>
 __global__ __launch_bounds__(kBlock)
-void k_adapt_rays(Frame Fin, InwScene S, const int2 *__restrict__ pixels, const float4 *__restrict__ aux,
+void k_adapt_rays(Frame Fin, InwScene S, const PassEntry<TL> *__restrict__ pixels, const float4 *__restrict__ aux,
                   uint32_t stop, uint32_t ns, uint32_t n, float4 *__restrict__ rays) {
     const uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
     if (i >= n) return;
     Frame F{};
-    pass_frame(F, Fin);
+    pass_frame_of<TL>(F, Fin);
     const uint32_t k = i / ns, j = i - k * ns;
-    const int2 p = pixels[k];
+    const Entry p = entry_of<TL>(F, pixels[k]);
     float4 *r = rays + 2 * (size_t)i;
     uint32_t s = 0xffffffffu;
-    if (listed(F, p)) {
-        const uint32_t c = aux_count(aux, (size_t)p.y * F.W + p.x);
+    if (p.listed) {
+        const uint32_t c = aux_count(aux, entry_index<TL>(F, p));
         if (c < stop && j < stop - c) s = c + j;
     }
     if (s != 0xffffffffu) pass_ray_record(S, F, p.x, p.y, s, r);
@@ -56,17 +80,18 @@ void k_adapt_rays(Frame Fin, InwScene S, const int2 *__restrict__ pixels, const 
 // even; the depth of sample spp / 2 -- and the state, the aux and the new count back.  last: the chunk is
 // the pass's last, and the image acc * RN(1 / count) and the depth are written (also for an entry that had
 // nothing left to render).
+template <bool TL>
 __global__ __launch_bounds__(kBlock)
-void k_adapt_fold(Frame Fin, const int2 *__restrict__ pixels, uint32_t n_pixels, uint32_t stop, uint32_t ns,
+void k_adapt_fold(Frame Fin, const PassEntry<TL> *__restrict__ pixels, uint32_t n_pixels, uint32_t stop, uint32_t ns,
                   uint32_t last, const float4 *__restrict__ out, float4 *__restrict__ state,
                   float4 *__restrict__ aux) {
     const uint32_t k = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
     if (k >= n_pixels) return;
     Frame F{};
-    pass_frame(F, Fin);
-    const int2 p = pixels[k];
-    if (!listed(F, p)) return;
-    const size_t o = (size_t)p.y * F.W + p.x;
+    pass_frame_of<TL>(F, Fin);
+    const Entry p = entry_of<TL>(F, pixels[k]);
+    if (!p.listed) return;
+    const size_t o = entry_index<TL>(F, p);
     const uint32_t mid = (uint32_t)F.spp / 2u;
     const float4 x = aux[o];
     const uint32_t c = __float_as_uint(x.w);
@@ -95,12 +120,13 @@ void k_adapt_fold(Frame Fin, const int2 *__restrict__ pixels, uint32_t n_pixels,
 // ------------------------------------------------------------------------------------------ IOW-03
 // The shared loop over the list: a lane's samples are [count, min(count + ns, stop)); an entry with
 // nothing left has its image rewritten from its state.
-template <bool LN>
+template <bool LN, bool TL>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPassIowWaves<LN>)))
-void k_iow_adapt(Frame Fin, IowScene S, const int2 *__restrict__ pixels, uint32_t stop, uint32_t ns,
+void k_iow_adapt(Frame Fin, IowScene S, const PassEntry<TL> *__restrict__ pixels, uint32_t stop, uint32_t ns,
                  float4 *__restrict__ state, float4 *__restrict__ aux, unsigned *queue, uint32_t rounds,
                  uint32_t n_units) {
-    iow_pass_loop<LN>(Fin, S, ListPass{pixels, aux, stop, ns}, state, queue, rounds, n_units);
+    using Src = std::conditional_t<TL, SlotPass, ListPass>;
+    iow_pass_loop<LN>(Fin, S, Src{pixels, aux, stop, ns}, state, queue, rounds, n_units);
 }
 
 // ------------------------------------------------------------------------------------------ select
@@ -124,24 +150,28 @@ __device__ __forceinline__ bool select_active(const Select &Q, size_t o, float &
     }
     return n < Q.stop && (n < Q.min_samples || !(err <= Q.tol));
 }
-// the rectangle of a frame for unit_pixel, everything else 0
+// the rectangle of a frame for unit_pixel, or (TL) its packed tile list, everything else 0
+template <bool TL>
 __device__ __forceinline__ void select_frame(Frame &F, const Frame &in) {
     F.W = in.W; F.H = in.H;
-    F.x0 = in.x0; F.y0 = in.y0; F.tw = in.tw; F.th = in.th;
+    if (TL) { F.tiles = in.tiles; F.n_tiles = in.n_tiles; F.tile_size = in.tile_size; }
+    else { F.x0 = in.x0; F.y0 = in.y0; F.tw = in.tw; F.th = in.th; }
 }
 
 constexpr int kSelWaves = kBlock / 64;
 
 // 1: a lane per unit, a block's (active, inactive) counts into part[block]; the error image.
+// TL, here and in the scatter: the units of a packed tile list, state, aux and err indexed by slot.
+template <bool TL>
 __global__ __launch_bounds__(kBlock)
 void k_select_count(Frame Fin, Select Q, uint32_t n_units, uint2 *__restrict__ part, float *__restrict__ d_err) {
     __shared__ uint2 s_cnt[kSelWaves];
     Frame F{};
-    select_frame(F, Fin);
+    select_frame<TL>(F, Fin);
     const uint32_t u = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
     bool in = false, act = false;
     if (u < n_units) {
-        const UnitPix p = unit_pixel(F, u);
+        const UnitPix p = pass_unit_pixel<TL>(F, u);
         if (p.in_image) {
             float err;
             in = true;
@@ -191,23 +221,36 @@ void k_select_scan(uint2 *__restrict__ part, uint32_t n, uint32_t *__restrict__ 
 }
 
 // 3: the scatter: an active unit's pixel at its active rank, an inactive one's {-1, -1} at the active
-// total + its inactive rank (so the list's tail, up to the rectangle's pixel count, is padding).
+// total + its inactive rank (so the list's tail, up to the rectangle's pixel count, is padding).  TL: the
+// slots, and 0xffffffff for the padding.
+template <bool TL>
+__device__ __forceinline__ PassEntry<TL> select_entry(const UnitPix &p) {
+    if constexpr (TL) return (uint32_t)p.out;
+    else return make_int2(p.x, p.y);
+}
+template <bool TL>
+__device__ __forceinline__ PassEntry<TL> select_none() {
+    if constexpr (TL) return kSlotNone;
+    else return make_int2(-1, -1);
+}
+
+template <bool TL>
 __global__ __launch_bounds__(kBlock)
 void k_select_scatter(Frame Fin, Select Q, uint32_t n_units, uint32_t n_blocks, const uint2 *__restrict__ part,
-                      int2 *__restrict__ list) {
+                      PassEntry<TL> *__restrict__ list) {
     __shared__ uint2 s_cnt[kSelWaves];
     Frame F{};
-    select_frame(F, Fin);
+    select_frame<TL>(F, Fin);
     const uint32_t u = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
     bool in = false, act = false;
-    int2 px = make_int2(-1, -1);
+    PassEntry<TL> px = select_none<TL>();
     if (u < n_units) {
-        const UnitPix p = unit_pixel(F, u);
+        const UnitPix p = pass_unit_pixel<TL>(F, u);
         if (p.in_image) {
             float err;
             in = true;
             act = select_active(Q, p.out, err);
-            px = make_int2(p.x, p.y);
+            px = select_entry<TL>(p);
         }
     }
     const unsigned long long ma = __ballot(act), mi = __ballot(in && !act);
@@ -219,7 +262,7 @@ void k_select_scatter(Frame Fin, Select Q, uint32_t n_units, uint32_t n_blocks, 
         if (w < wave) { off.x += s_cnt[w].x; off.y += s_cnt[w].y; }
     const uint32_t total = part[n_blocks].x;
     if (act) list[off.x + lanes_below(ma)] = px;
-    else if (in) list[total + off.y + lanes_below(mi)] = make_int2(-1, -1);
+    else if (in) list[total + off.y + lanes_below(mi)] = select_none<TL>();
 }
 
 // ------------------------------------------------------------------------------------------ launch
@@ -231,22 +274,71 @@ hipError_t adapt_info(Kn kernel, int info[4]) {
     return kernel_info(kernel, occupancy_of(kernel, kBlock), info);
 }
 // resident blocks per CU of the instance a scene runs, asked once each
-int iow_adapt_blocks(bool ln) {
-    static const int nb[2] = {occupancy_of(k_iow_adapt<false>, kBlock), occupancy_of(k_iow_adapt<true>, kBlock)};
-    return nb[ln ? 1 : 0];
+int iow_adapt_blocks(bool ln, bool tl) {
+    static const int nb[4] = {occupancy_of(k_iow_adapt<false, false>, kBlock), occupancy_of(k_iow_adapt<true, false>, kBlock),
+                              occupancy_of(k_iow_adapt<false, true>, kBlock), occupancy_of(k_iow_adapt<true, true>, kBlock)};
+    return nb[(tl ? 2 : 0) + (ln ? 1 : 0)];
 }
 dim3 lanes_grid(uint32_t n) { return dim3((n + (uint32_t)kBlock - 1u) / (uint32_t)kBlock); }
+
+// The launches, one body for the pixel list (TL = false) and the slot list of f's packed tile list.
+template <bool TL>
+hipError_t adapt_rays(const Frame &f, const InwScene &sc, const PassEntry<TL> *list, uint32_t n_list, const float4 *aux,
+                      uint32_t stop, uint32_t ns, float4 *rays, hipStream_t s) {
+    const uint32_t n = n_list * ns;  // <= 2^31 (the caller's chunks)
+    hipLaunchKernelGGL(k_adapt_rays<TL>, lanes_grid(n), dim3(kBlock), 0, s, f, sc, list, aux, stop, ns, n, rays);
+    return hipGetLastError();
+}
+
+template <bool TL>
+hipError_t adapt_fold(const Frame &f, const PassEntry<TL> *list, uint32_t n_list, uint32_t stop, uint32_t ns, bool last,
+                      const float4 *out, float4 *state, float4 *aux, hipStream_t s) {
+    hipLaunchKernelGGL(k_adapt_fold<TL>, lanes_grid(n_list), dim3(kBlock), 0, s, f, list, n_list, stop, ns,
+                       last ? 1u : 0u, out, state, aux);
+    return hipGetLastError();
+}
+
+template <bool TL>
+hipError_t iow_adapt(const Frame &f, const IowScene &sc, const PassEntry<TL> *list, uint32_t n_list, uint32_t stop,
+                     uint32_t ns, float4 *state, float4 *aux, unsigned *queue, int cus, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(queue, 0, sizeof(unsigned), s);
+    if (e != hipSuccess) return e;
+    const bool ln = iow_lds(sc);
+    const ClaimGrid cg = claim_grid(n_list, cus, iow_adapt_blocks(ln, TL), pass_max_blocks_now());
+    const dim3 g(cg.grid), b(kBlock);
+    if (ln) hipLaunchKernelGGL((k_iow_adapt<true, TL>), g, b, 0, s, f, sc, list, stop, ns, state, aux, queue, cg.rounds, n_list);
+    else hipLaunchKernelGGL((k_iow_adapt<false, TL>), g, b, 0, s, f, sc, list, stop, ns, state, aux, queue, cg.rounds, n_list);
+    return hipGetLastError();
+}
+
+template <bool TL>
+hipError_t pass_select(const Frame &f, const float4 *state, const float4 *aux, float tol, uint32_t min_samples,
+                       uint32_t stop, PassEntry<TL> *list, uint32_t *n_active, float *err, uint2 *part, hipStream_t s) {
+    const uint32_t n_units = units_of(f), n_blocks = select_blocks(f);
+    const Select q{state, aux, tol, min_samples, stop};
+    const dim3 g(n_blocks), b(kBlock);
+    hipLaunchKernelGGL(k_select_count<TL>, g, b, 0, s, f, q, n_units, part, err);
+    hipLaunchKernelGGL(k_select_scan, dim3(1), b, 0, s, part, n_blocks, n_active);
+    hipLaunchKernelGGL(k_select_scatter<TL>, g, b, 0, s, f, q, n_units, n_blocks, part, list);
+    return hipGetLastError();
+}
 }  // namespace
 
 hipError_t adaptive_kernel_info(int which, int info[4]) {
     switch (which) {
-        case 0: return adapt_info(k_adapt_rays, info);
-        case 1: return adapt_info(k_adapt_fold, info);
-        case 2: return adapt_info(k_iow_adapt<true>, info);
-        case 3: return adapt_info(k_iow_adapt<false>, info);
-        case 4: return adapt_info(k_select_count, info);
+        case 0: return adapt_info(k_adapt_rays<false>, info);
+        case 1: return adapt_info(k_adapt_fold<false>, info);
+        case 2: return adapt_info(k_iow_adapt<true, false>, info);
+        case 3: return adapt_info(k_iow_adapt<false, false>, info);
+        case 4: return adapt_info(k_select_count<false>, info);
         case 5: return adapt_info(k_select_scan, info);
-        case 6: return adapt_info(k_select_scatter, info);
+        case 6: return adapt_info(k_select_scatter<false>, info);
+        case 7: return adapt_info(k_adapt_rays<true>, info);  // the tile-list instances
+        case 8: return adapt_info(k_adapt_fold<true>, info);
+        case 9: return adapt_info(k_iow_adapt<true, true>, info);
+        case 10: return adapt_info(k_iow_adapt<false, true>, info);
+        case 11: return adapt_info(k_select_count<true>, info);
+        case 12: return adapt_info(k_select_scatter<true>, info);
     }
     return hipErrorInvalidValue;
 }
@@ -261,41 +353,40 @@ int adaptive_chunk_cap(int samples) {
 
 hipError_t launch_adapt_rays(const Frame &f, const InwScene &sc, const int2 *pixels, uint32_t n_pixels,
                              const float4 *aux, uint32_t stop, uint32_t ns, float4 *rays, hipStream_t s) {
-    const uint32_t n = n_pixels * ns;  // <= 2^31 (the caller's chunks)
-    hipLaunchKernelGGL(k_adapt_rays, lanes_grid(n), dim3(kBlock), 0, s, f, sc, pixels, aux, stop, ns, n, rays);
-    return hipGetLastError();
+    return adapt_rays<false>(f, sc, pixels, n_pixels, aux, stop, ns, rays, s);
+}
+hipError_t launch_adapt_rays(const Frame &f, const InwScene &sc, const uint32_t *slots, uint32_t n_slots,
+                             const float4 *aux, uint32_t stop, uint32_t ns, float4 *rays, hipStream_t s) {
+    return adapt_rays<true>(f, sc, slots, n_slots, aux, stop, ns, rays, s);
 }
 
 hipError_t launch_adapt_fold(const Frame &f, const int2 *pixels, uint32_t n_pixels, uint32_t stop, uint32_t ns,
                              bool last, const float4 *out, float4 *state, float4 *aux, hipStream_t s) {
-    hipLaunchKernelGGL(k_adapt_fold, lanes_grid(n_pixels), dim3(kBlock), 0, s, f, pixels, n_pixels, stop, ns,
-                       last ? 1u : 0u, out, state, aux);
-    return hipGetLastError();
+    return adapt_fold<false>(f, pixels, n_pixels, stop, ns, last, out, state, aux, s);
+}
+hipError_t launch_adapt_fold(const Frame &f, const uint32_t *slots, uint32_t n_slots, uint32_t stop, uint32_t ns,
+                             bool last, const float4 *out, float4 *state, float4 *aux, hipStream_t s) {
+    return adapt_fold<true>(f, slots, n_slots, stop, ns, last, out, state, aux, s);
 }
 
 hipError_t launch_iow_adapt(const Frame &f, const IowScene &sc, const int2 *pixels, uint32_t n_pixels, uint32_t stop,
                             uint32_t ns, float4 *state, float4 *aux, unsigned *queue, int cus, hipStream_t s) {
-    const hipError_t e = hipMemsetAsync(queue, 0, sizeof(unsigned), s);
-    if (e != hipSuccess) return e;
-    const bool ln = iow_lds(sc);
-    const ClaimGrid cg = claim_grid(n_pixels, cus, iow_adapt_blocks(ln), pass_max_blocks_now());
-    const dim3 g(cg.grid), b(kBlock);
-    if (ln) hipLaunchKernelGGL((k_iow_adapt<true>), g, b, 0, s, f, sc, pixels, stop, ns, state, aux, queue, cg.rounds, n_pixels);
-    else hipLaunchKernelGGL((k_iow_adapt<false>), g, b, 0, s, f, sc, pixels, stop, ns, state, aux, queue, cg.rounds, n_pixels);
-    return hipGetLastError();
+    return iow_adapt<false>(f, sc, pixels, n_pixels, stop, ns, state, aux, queue, cus, s);
+}
+hipError_t launch_iow_adapt(const Frame &f, const IowScene &sc, const uint32_t *slots, uint32_t n_slots, uint32_t stop,
+                            uint32_t ns, float4 *state, float4 *aux, unsigned *queue, int cus, hipStream_t s) {
+    return iow_adapt<true>(f, sc, slots, n_slots, stop, ns, state, aux, queue, cus, s);
 }
 
 uint32_t select_blocks(const Frame &f) { return (units_of(f) + (uint32_t)kBlock - 1u) / (uint32_t)kBlock; }
 
 hipError_t launch_pass_select(const Frame &f, const float4 *state, const float4 *aux, float tol, uint32_t min_samples,
                               uint32_t stop, int2 *list, uint32_t *n_active, float *err, uint2 *part, hipStream_t s) {
-    const uint32_t n_units = units_of(f), n_blocks = select_blocks(f);
-    const Select q{state, aux, tol, min_samples, stop};
-    const dim3 g(n_blocks), b(kBlock);
-    hipLaunchKernelGGL(k_select_count, g, b, 0, s, f, q, n_units, part, err);
-    hipLaunchKernelGGL(k_select_scan, dim3(1), b, 0, s, part, n_blocks, n_active);
-    hipLaunchKernelGGL(k_select_scatter, g, b, 0, s, f, q, n_units, n_blocks, part, list);
-    return hipGetLastError();
+    return pass_select<false>(f, state, aux, tol, min_samples, stop, list, n_active, err, part, s);
+}
+hipError_t launch_pass_select(const Frame &f, const float4 *state, const float4 *aux, float tol, uint32_t min_samples,
+                              uint32_t stop, uint32_t *slots, uint32_t *n_active, float *err, uint2 *part, hipStream_t s) {
+    return pass_select<true>(f, state, aux, tol, min_samples, stop, slots, n_active, err, part, s);
 }
 
 }  // namespace rtk

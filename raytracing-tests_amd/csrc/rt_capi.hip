@@ -231,6 +231,12 @@ bool cuts_ok(const rt_params *p, const uint32_t *cuts, int n_cuts) {
     return true;
 }
 
+// A packed tile list of the adaptive calls: rt_render_pass_tiles_async's rule, at most 2^31 slots.
+bool tile_list_ok(const int *d_tiles, int n_tiles, int tile_size) {
+    if (!d_tiles || n_tiles <= 0 || tile_size <= 0 || tile_size % 16 != 0) return false;
+    return uint64_t(n_tiles) * uint64_t(tile_size) * uint64_t(tile_size) <= (uint64_t(1) << 31);
+}
+
 // The blocking passes: a temporary scene from make(scene), the host buffers up (pixels outside the
 // rectangle keep their bytes), pass i = samples [cuts[i - 1], cuts[i]) into image i, timed together
 // on the null stream, the images, the last state and the counters back.
@@ -1103,6 +1109,61 @@ int rt_pass_select_async(rt_dev_scene *s, const rt_params *p, const rt_pass_stat
     const hipError_t e = rtk::launch_pass_select(f, reinterpret_cast<const float4 *>(d_state),
                                                  reinterpret_cast<const float4 *>(d_aux), tol, min_samples, pass_stop(s),
                                                  reinterpret_cast<int2 *>(d_list), d_n_active, d_err,
+                                                 s->select_ws.as<uint2>(), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RT_OK : launch_failed(e);
+}
+
+// The adaptive pair on a packed tile list: the same launches with the list entries slots and everything
+// indexed by slot (the kernels' tile-list instances).
+int rt_render_pass_slots_async(rt_dev_scene *s, const rt_camera *cam, const rt_params *p, const int *d_tiles,
+                               int n_tiles, int tile_size, const uint32_t *d_slots, uint32_t n_slots, uint32_t ns,
+                               rt_pass_state *d_state_packed, rt_pass_aux *d_aux_packed, float *d_out_packed,
+                               float *d_out_depth_packed, uint64_t *d_counters, void *stream) {
+    if (!s || !cam || !params_ok(p) || !d_state_packed || !d_aux_packed || p->spp != s->spp || s->broken)
+        return RT_E_ARG;
+    if (!tile_list_ok(d_tiles, n_tiles, tile_size)) return RT_E_ARG;
+    if (n_slots > (1u << 31) || (n_slots > 0 && !d_slots)) return RT_E_ARG;
+    if (s->tex_missing) return RT_E_UNSUPPORTED;  // a textured object and no texture bound (rt_dev_scene_inw_update_device)
+    if (p->show_normal) return RT_E_UNSUPPORTED;  // one normal per sample, no fold state
+    if (n_slots == 0 || ns == 0) return RT_OK;
+    const uint32_t stop = pass_stop(s);
+    ns = std::min(ns, stop);  // no slot has more samples left
+    rt_params whole = *p;
+    whole.tile_x0 = whole.tile_y0 = whole.tile_w = whole.tile_h = 0;  // the list says which pixels
+    rtk::Frame f = make_pass_frame(s, cam, &whole, d_out_packed, d_out_depth_packed, d_counters);
+    f.tiles = d_tiles; f.n_tiles = n_tiles; f.tile_size = tile_size;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    float4 *state = reinterpret_cast<float4 *>(d_state_packed), *aux = reinterpret_cast<float4 *>(d_aux_packed);
+    if (s->kind == 3) {
+        unsigned *queue = s->counter.as<unsigned>() + 192;  // the passes' own: calls on one scene do not overlap
+        const hipError_t e = rtk::launch_iow_adapt(f, iow_view(*s), d_slots, n_slots, stop, ns, state, aux, queue, s->cus, st);
+        return e == hipSuccess ? RT_OK : launch_failed(e);
+    }
+    return pass_inw_chunks(s, cam, p, n_slots, ns, rtk::adaptive_chunk_cap_now(), d_counters, st,
+        [&](const rtk::InwScene &sc, uint32_t, uint32_t nsc, float4 *rays) {
+            return rtk::launch_adapt_rays(f, sc, d_slots, n_slots, aux, stop, nsc, rays, st);
+        },
+        [&](uint32_t, uint32_t nsc, bool last, const float4 *out) {
+            return rtk::launch_adapt_fold(f, d_slots, n_slots, stop, nsc, last, out, state, aux, st);
+        });
+}
+
+int rt_pass_select_tiles_async(rt_dev_scene *s, const rt_params *p, const int *d_tiles, int n_tiles, int tile_size,
+                               const rt_pass_state *d_state_packed, const rt_pass_aux *d_aux_packed, float tol,
+                               uint32_t min_samples, uint32_t *d_slots, uint32_t *d_n_active, float *d_err_packed,
+                               void *stream) {
+    if (!s || !params_ok(p) || !d_state_packed || !d_aux_packed || !d_slots || !d_n_active || p->spp != s->spp ||
+        s->broken)
+        return RT_E_ARG;
+    if (!tile_list_ok(d_tiles, n_tiles, tile_size)) return RT_E_ARG;
+    if (s->tex_missing) return RT_E_UNSUPPORTED;  // a textured object and no texture bound (rt_dev_scene_inw_update_device)
+    if (p->show_normal) return RT_E_UNSUPPORTED;  // one normal per sample, no fold state
+    rtk::Frame f = make_frame(nullptr, p);
+    f.tiles = d_tiles; f.n_tiles = n_tiles; f.tile_size = tile_size;
+    HIP_OK(s->select_ws.reserve((size_t(rtk::select_blocks(f)) + 1) * sizeof(uint2)));
+    const hipError_t e = rtk::launch_pass_select(f, reinterpret_cast<const float4 *>(d_state_packed),
+                                                 reinterpret_cast<const float4 *>(d_aux_packed), tol, min_samples,
+                                                 pass_stop(s), d_slots, d_n_active, d_err_packed,
                                                  s->select_ws.as<uint2>(), static_cast<hipStream_t>(stream));
     return e == hipSuccess ? RT_OK : launch_failed(e);
 }

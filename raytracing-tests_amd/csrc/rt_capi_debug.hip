@@ -533,8 +533,12 @@ int rt_debug_pixels_kernel(int which, int info[4]) {
 }
 
 int rt_debug_pass_kernel(int which, int info[4]) {
-    if (!info || which < 0 || (which > 3 && which < 8) || which == 15 || which > 19) return RT_E_ARG;
-    if (which >= 16) HIP_OK(rtk::pass_kernel_info(which - 12, info));  // the tile-list instances
+    if (!info || which < 0 || (which > 3 && which < 8) || which == 15 || (which > 19 && which < 24) || which == 29 ||
+        which > 30)
+        return RT_E_ARG;
+    // rt_adaptive.hip's tile-list instances: an adaptive kernel's `which` + 16 (the scan, 13, serves both)
+    if (which >= 24) HIP_OK(rtk::adaptive_kernel_info(which == 30 ? 12 : which - 17, info));
+    else if (which >= 16) HIP_OK(rtk::pass_kernel_info(which - 12, info));  // the tile-list instances
     else if (which >= 8) HIP_OK(rtk::adaptive_kernel_info(which - 8, info));  // rt_adaptive.hip's
     else HIP_OK(rtk::pass_kernel_info(which, info));
     return RT_OK;

@@ -541,9 +541,17 @@ hipError_t launch_adapt_rays(const Frame &f, const InwScene &sc, const int2 *pix
                              const float4 *aux, uint32_t stop, uint32_t ns, float4 *rays, hipStream_t s);
 hipError_t launch_adapt_fold(const Frame &f, const int2 *pixels, uint32_t n_pixels, uint32_t stop, uint32_t ns,
                              bool last, const float4 *out, float4 *state, float4 *aux, hipStream_t s);
+// The same pair over a slot list of f's packed tile list (f.tiles set; a slot = tile * T * T + iy * T + ix, one
+// that is 0xffffffff, past the list's slots or outside the image is skipped): state, aux, image and answers by slot.
+hipError_t launch_adapt_rays(const Frame &f, const InwScene &sc, const uint32_t *slots, uint32_t n_slots,
+                             const float4 *aux, uint32_t stop, uint32_t ns, float4 *rays, hipStream_t s);
+hipError_t launch_adapt_fold(const Frame &f, const uint32_t *slots, uint32_t n_slots, uint32_t stop, uint32_t ns,
+                             bool last, const float4 *out, float4 *state, float4 *aux, hipStream_t s);
 // IOW-03: launch_iow_pass's persistent grid over the list (queue: one u32, zeroed here; pass_max_blocks caps
 // the grid).
 hipError_t launch_iow_adapt(const Frame &f, const IowScene &sc, const int2 *pixels, uint32_t n_pixels, uint32_t stop,
+                            uint32_t ns, float4 *state, float4 *aux, unsigned *queue, int cus, hipStream_t s);
+hipError_t launch_iow_adapt(const Frame &f, const IowScene &sc, const uint32_t *slots, uint32_t n_slots, uint32_t stop,
                             uint32_t ns, float4 *state, float4 *aux, unsigned *queue, int cus, hipStream_t s);
 // The stable partition of the units of f's rectangle into the active pixels, in unit order, and a tail of
 // {-1, -1} up to the rectangle's pixel count; *n_active = the active count; err (W x H, may be null): the
@@ -551,8 +559,13 @@ hipError_t launch_iow_adapt(const Frame &f, const IowScene &sc, const int2 *pixe
 uint32_t select_blocks(const Frame &f);
 hipError_t launch_pass_select(const Frame &f, const float4 *state, const float4 *aux, float tol, uint32_t min_samples,
                               uint32_t stop, int2 *list, uint32_t *n_active, float *err, uint2 *part, hipStream_t s);
+// The same over the units of f's packed tile list (f.tiles set): the active slots in unit order, a tail of
+// 0xffffffff up to the number of slots inside the image; state, aux and err by slot.
+hipError_t launch_pass_select(const Frame &f, const float4 *state, const float4 *aux, float tol, uint32_t min_samples,
+                              uint32_t stop, uint32_t *slots, uint32_t *n_active, float *err, uint2 *part, hipStream_t s);
 // {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of k_adapt_rays (which = 0), k_adapt_fold
-// (1), k_iow_adapt (2 nodes staged in LDS, 3 not), k_select_count (4), k_select_scan (5), k_select_scatter (6)
+// (1), k_iow_adapt (2 nodes staged in LDS, 3 not), k_select_count (4), k_select_scan (5), k_select_scatter (6);
+// 7..12: the tile-list instances of 0..4 and 6 (the scan is shared)
 hipError_t adaptive_kernel_info(int which, int info[4]);
 int adaptive_chunk_cap_now();          // the cap rt_debug_adaptive_chunk set (0 = none)
 int adaptive_chunk_cap(int samples);   // rt_debug_adaptive_chunk: cap an INW chunk's samples (0 = off); the previous cap

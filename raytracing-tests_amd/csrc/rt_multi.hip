@@ -11,6 +11,10 @@
 // Progressive frames (rt_render_pass_multi_async): every device keeps the fold state of its share's slots
 // and continues it with rt_render_pass_tiles_async; a pass that is asked for an image ends in the same
 // exchange and unpack, one that is not sends its counters alone.
+// Adaptive frames (rt_render_adaptive_multi_async): beside the states every device keeps the aux records, a
+// slot list and packed image buffers of the adaptive frame; a round is rt_render_pass_slots_async over the
+// list, rt_pass_select_tiles_async for the next list, the active count to pinned host memory behind an event,
+// and the same exchange.  The next round waits for the counts on the host and sizes its launches by them.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -43,6 +47,26 @@ __global__ __launch_bounds__(256) void k_unpack_tiles(const float4 *recv, const 
     const size_t o = size_t(y) * size_t(W) + size_t(x);
     rgba[o] = recv[i];
     if (depth) depth[o] = recv_depth[i];
+}
+
+// The sample counts of a share's slots out of its aux records (rt_pass_aux: even.xyz, count), one thread a slot.
+__global__ __launch_bounds__(256) void k_aux_counts(const uint4 *aux, uint32_t n, uint32_t *counts) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;  // no cross-lane work in this kernel
+    counts[i] = aux[i].w;
+}
+
+// k_unpack_tiles for the gathered counts: d_count[y * W + x] of the slots inside the image.
+__global__ __launch_bounds__(256) void k_unpack_counts(const uint32_t *recv, const int2 *tiles, uint32_t n_px, int T,
+                                                       int W, int H, uint32_t *count) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_px) return;  // no cross-lane work in this kernel
+    const uint32_t area = uint32_t(T) * uint32_t(T);
+    const int2 t = tiles[i / area];
+    const uint32_t r = i % area;
+    const int x = t.x * T + int(r % uint32_t(T)), y = t.y * T + int(r / uint32_t(T));
+    if (x >= W || y >= H) return;
+    count[size_t(y) * size_t(W) + size_t(x)] = recv[i];
 }
 
 // d_counters[k] += sum over devices of their 6 counters (one 64-lane block)
@@ -117,14 +141,28 @@ struct rt_group {
         Buf tiles, packed, depth, counters;
         Buf state;  // the fold state of the share's slots (rt_pass_state, 32 B each): it never leaves its device
         int n_tiles = 0;
+        // the adaptive frame (rt_render_adaptive_multi_async), allocated when the deal's first one begins:
+        // the aux records beside the states, the slot list and its active count, the counts as they travel,
+        // and packed image and depth buffers of its own, which rt_render_multi_async never writes
+        Buf aux, slots, n_active, counts, a_packed, a_depth;
+        uint32_t n_inside = 0;       // the share's slots inside the image
+        hipEvent_t counted = nullptr;  // behind the copy of n_active to the group's pinned counts
     };
     std::vector<std::unique_ptr<Share>> share;
-    Buf recv, recv_depth, recv_tiles, recv_ctr;  // on device 0
+    Buf recv, recv_depth, recv_tiles, recv_ctr, recv_count;  // on device 0
     // the deal the buffers hold (re-uploaded when the frame or tile size changes)
     int W = 0, H = 0, T = 0;
     std::vector<uint32_t> off;  // device r's first tile in the gathered order
     uint32_t samples = 0;       // rt_render_pass_multi_async: the samples the states hold for this deal
+    bool adaptive = false;      // the states of this deal were left by an adaptive round, and no pass ran since
+    uint32_t *h_active = nullptr;  // pinned: device r's active count of the last adaptive round
     ~rt_group() {
+        for (size_t r = 0; r < share.size(); r++)
+            if (share[r]->counted) {
+                (void)hipSetDevice(dev[r]);
+                (void)hipEventDestroy(share[r]->counted);
+            }
+        if (h_active) (void)hipHostFree(h_active);
         share.clear();
         for (ncclComm_t c : comm)
             if (c) (void)ncclCommDestroy(c);
@@ -145,6 +183,7 @@ namespace {
 int set_deal(rt_group *g, int W, int H, int T, hipStream_t s0) {
     if (g->W == W && g->H == H && g->T == T) return RT_OK;
     g->samples = 0;  // the states of another deal are no one's
+    g->adaptive = false;
     for (int r = 0; r < g->n; r++) {
         MULTI_HIP(hipSetDevice(g->dev[size_t(r)]));
         MULTI_HIP(hipStreamSynchronize(r == 0 ? s0 : g->st[size_t(r)]));
@@ -162,6 +201,10 @@ int set_deal(rt_group *g, int W, int H, int T, hipStream_t s0) {
     for (int r = 0; r < g->n; r++) {
         auto &S = *g->share[size_t(r)];
         S.n_tiles = int(lists[size_t(r)].size() / 2);
+        S.n_inside = 0;
+        for (int k = 0; k < S.n_tiles; k++)
+            S.n_inside += uint32_t(std::min(T, W - lists[size_t(r)][size_t(2 * k)] * T)) *
+                          uint32_t(std::min(T, H - lists[size_t(r)][size_t(2 * k + 1)] * T));
         g->off[size_t(r) + 1] = g->off[size_t(r)] + uint32_t(S.n_tiles);
         all.insert(all.end(), lists[size_t(r)].begin(), lists[size_t(r)].end());
         MULTI_HIP(hipSetDevice(g->dev[size_t(r)]));
@@ -190,8 +233,9 @@ int set_deal(rt_group *g, int W, int H, int T, hipStream_t s0) {
 // device 0 (device 0 sends to itself too, so one code path serves every group size), where one kernel
 // unpacks the tiles into the W x H image and one adds the counters up.  An error inside the group still
 // ends it, so later RCCL calls of this thread are not left inside an open group.
+// adaptive: the packed image and depth are the adaptive frame's, and with d_count the counts travel too.
 int gather(rt_group *g, const rt_params *p, int tile_size, bool image, float *d_rgba, float *d_depth,
-           uint64_t *d_counters, hipStream_t s0) {
+           uint64_t *d_counters, hipStream_t s0, bool adaptive = false, uint32_t *d_count = nullptr) {
     auto stream_of = [&](int r) { return r == 0 ? s0 : g->st[size_t(r)]; };
     const size_t area = size_t(tile_size) * size_t(tile_size);
     MULTI_NCCL(ncclGroupStart());
@@ -200,10 +244,14 @@ int gather(rt_group *g, const rt_params *p, int tile_size, bool image, float *d_
     for (int r = 0; r < g->n && nr == ncclSuccess; r++) {
         auto &S = *g->share[size_t(r)];
         if (S.n_tiles && image) {
-            call(ncclSend(S.packed.p, size_t(S.n_tiles) * area * 4, ncclFloat32, 0, g->comm[size_t(r)], stream_of(r)));
+            call(ncclSend(adaptive ? S.a_packed.p : S.packed.p, size_t(S.n_tiles) * area * 4, ncclFloat32, 0,
+                          g->comm[size_t(r)], stream_of(r)));
             if (d_depth)
-                call(ncclSend(S.depth.p, size_t(S.n_tiles) * area, ncclFloat32, 0, g->comm[size_t(r)], stream_of(r)));
+                call(ncclSend(adaptive ? S.a_depth.p : S.depth.p, size_t(S.n_tiles) * area, ncclFloat32, 0,
+                              g->comm[size_t(r)], stream_of(r)));
         }
+        if (S.n_tiles && d_count)
+            call(ncclSend(S.counts.p, size_t(S.n_tiles) * area, ncclUint32, 0, g->comm[size_t(r)], stream_of(r)));
         call(ncclSend(S.counters.p, 6, ncclUint64, 0, g->comm[size_t(r)], stream_of(r)));
     }
     for (int r = 0; r < g->n && nr == ncclSuccess; r++) {
@@ -216,6 +264,9 @@ int gather(rt_group *g, const rt_params *p, int tile_size, bool image, float *d_
                 call(ncclRecv(g->recv_depth.as<float>() + o * area, size_t(S.n_tiles) * area, ncclFloat32, r,
                               g->comm[0], s0));
         }
+        if (S.n_tiles && d_count)
+            call(ncclRecv(g->recv_count.as<uint32_t>() + o * area, size_t(S.n_tiles) * area, ncclUint32, r, g->comm[0],
+                          s0));
         call(ncclRecv(g->recv_ctr.as<unsigned long long>() + size_t(r) * 6, 6, ncclUint64, r, g->comm[0], s0));
     }
     const ncclResult_t ne = ncclGroupEnd();
@@ -228,10 +279,40 @@ int gather(rt_group *g, const rt_params *p, int tile_size, bool image, float *d_
         hipLaunchKernelGGL(k_unpack_tiles, dim3((n_px + 255u) / 256u), dim3(256), 0, s0, g->recv.as<float4>(),
                            g->recv_depth.as<float>(), g->recv_tiles.as<int2>(), n_px, tile_size, p->width, p->height,
                            reinterpret_cast<float4 *>(d_rgba), d_depth);
+    if (n_px && d_count)
+        hipLaunchKernelGGL(k_unpack_counts, dim3((n_px + 255u) / 256u), dim3(256), 0, s0, g->recv_count.as<uint32_t>(),
+                           g->recv_tiles.as<int2>(), n_px, tile_size, p->width, p->height, d_count);
     if (d_counters)
         hipLaunchKernelGGL(k_sum_counters, dim3(1), dim3(64), 0, s0, g->recv_ctr.as<unsigned long long>(), g->n,
                            reinterpret_cast<unsigned long long *>(d_counters));
     MULTI_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+// The adaptive frame's buffers of the current deal, the pinned counts and the events: allocated when the
+// deal's first adaptive frame begins, kept while the deal stays.
+int ensure_adaptive(rt_group *g) {
+    if (!g->h_active) {
+        MULTI_HIP(hipHostMalloc(reinterpret_cast<void **>(&g->h_active), size_t(g->n) * sizeof(uint32_t),
+                                hipHostMallocPortable));  // every device of the group copies into it
+        std::memset(g->h_active, 0, size_t(g->n) * sizeof(uint32_t));
+    }
+    const size_t area = size_t(g->T) * size_t(g->T);
+    for (int r = 0; r < g->n; r++) {
+        auto &S = *g->share[size_t(r)];
+        const int d = g->dev[size_t(r)];
+        MULTI_HIP(hipSetDevice(d));
+        if (!S.counted) MULTI_HIP(hipEventCreateWithFlags(&S.counted, hipEventDisableTiming));
+        const size_t slots = size_t(std::max(S.n_tiles, 1)) * area;
+        MULTI_HIP(S.aux.ensure(slots * sizeof(rt_pass_aux), d));
+        MULTI_HIP(S.slots.ensure(slots * sizeof(uint32_t), d));
+        MULTI_HIP(S.n_active.ensure(sizeof(uint32_t), d));
+        MULTI_HIP(S.counts.ensure(slots * sizeof(uint32_t), d));
+        MULTI_HIP(S.a_packed.ensure(slots * 4 * sizeof(float), d));
+        MULTI_HIP(S.a_depth.ensure(slots * sizeof(float), d));
+    }
+    MULTI_HIP(hipSetDevice(g->dev[0]));
+    MULTI_HIP(g->recv_count.ensure(size_t(g->off[size_t(g->n)]) * area * sizeof(uint32_t), g->dev[0]));
     return RT_OK;
 }
 
@@ -421,6 +502,7 @@ int rt_render_pass_multi_async(rt_group *g, rt_dev_scene *const *scenes, const r
     auto stream_of = [&](int r) { return r == 0 ? st0 : g->st[size_t(r)]; };
     const bool image = d_rgba != nullptr, want_depth = image && d_depth != nullptr;
     g->samples = 0;  // until every device has taken the pass: a failed one leaves states of no count
+    g->adaptive = false;  // and no adaptive round continues them
     // every device continues the states of its share on its own stream
     for (int r = 0; r < g->n; r++) {
         auto &S = *g->share[size_t(r)];
@@ -436,6 +518,96 @@ int rt_render_pass_multi_async(rt_group *g, rt_dev_scene *const *scenes, const r
     const int rc = gather(g, p, tile_size, image, d_rgba, want_depth ? d_depth : nullptr, d_counters, st0);
     if (rc == RT_OK) g->samples = uint32_t(std::min<uint64_t>(uint64_t(s0) + ns, uint64_t(p->spp)));
     return rc;
+}
+
+int rt_render_adaptive_multi_async(rt_group *g, rt_dev_scene *const *scenes, const rt_camera *cam, const rt_params *p,
+                                   int tile_size, int first, uint32_t ns, float tol, uint32_t min_samples,
+                                   float *d_rgba, float *d_depth, uint32_t *d_count, uint64_t *d_counters,
+                                   void *stream) {
+    if (!g || !scenes || !cam || !p || p->width <= 0 || p->height <= 0 || p->spp < 1 || p->max_bounces < 0 ||
+        tile_size <= 0 || tile_size % 16 != 0)
+        return RT_E_ARG;
+    if (!scenes_ok(g, scenes)) return RT_E_ARG;
+    // as in rt_render_pass_multi_async, every scene is asked before the group is touched
+    bool unsupported = p->show_normal != 0;
+    for (int r = 0; r < g->n; r++) {
+        const int rc = rtamd::scene_pass_check(scenes[r], p->spp);
+        if (rc == RT_E_ARG) return RT_E_ARG;
+        unsupported |= rc != RT_OK;
+    }
+    // a round continues the adaptive frame of this deal, which no pass has touched since
+    if (!first && !(g->adaptive && g->W == p->width && g->H == p->height && g->T == tile_size)) return RT_E_ARG;
+    if (unsupported) return RT_E_UNSUPPORTED;
+    if (ns == 0) return RT_OK;
+    DeviceGuard guard;
+    const hipStream_t st0 = static_cast<hipStream_t>(stream);
+    if (int rc = set_deal(g, p->width, p->height, tile_size, st0); rc != RT_OK) {
+        g->W = 0;  // rebuild the deal next time
+        return rc;
+    }
+    auto stream_of = [&](int r) { return r == 0 ? st0 : g->st[size_t(r)]; };
+    const bool image = d_rgba != nullptr, want_depth = image && d_depth != nullptr;
+    g->samples = 0;  // the states are an adaptive frame's: no progressive pass continues into them
+    g->adaptive = false;  // until every device has taken the round
+    if (first)
+        if (int rc = ensure_adaptive(g); rc != RT_OK) return rc;
+    const size_t area = size_t(tile_size) * size_t(tile_size);
+    for (int r = 0; r < g->n; r++) {
+        auto &S = *g->share[size_t(r)];
+        const hipStream_t sr = stream_of(r);
+        MULTI_HIP(hipSetDevice(g->dev[size_t(r)]));
+        MULTI_HIP(hipMemsetAsync(S.counters.p, 0, 6 * sizeof(unsigned long long), sr));
+        if (S.n_tiles == 0) continue;
+        const size_t slots = size_t(S.n_tiles) * area;
+        rt_pass_state *state = S.state.as<rt_pass_state>();
+        rt_pass_aux *aux = S.aux.as<rt_pass_aux>();
+        uint32_t n_list = 0;
+        if (first) {  // no samples anywhere, every slot inside the image listed (a select that finds all active)
+            MULTI_HIP(hipMemsetAsync(S.aux.p, 0, slots * sizeof(rt_pass_aux), sr));
+            MULTI_HIP(hipMemsetAsync(S.a_packed.p, 0, slots * 4 * sizeof(float), sr));
+            MULTI_HIP(hipMemsetAsync(S.a_depth.p, 0, slots * sizeof(float), sr));
+            const int rc = rt_pass_select_tiles_async(scenes[r], p, S.tiles.as<int>(), S.n_tiles, tile_size, state, aux,
+                                                      -1.0f, 0, S.slots.as<uint32_t>(), S.n_active.as<uint32_t>(),
+                                                      nullptr, sr);
+            if (rc != RT_OK) return rc;
+            n_list = S.n_inside;
+        } else {  // the one wait: the previous round's count sizes this round's launches
+            MULTI_HIP(hipEventSynchronize(S.counted));
+            n_list = g->h_active[r];
+        }
+        if (n_list != 0) {
+            int rc = rt_render_pass_slots_async(scenes[r], cam, p, S.tiles.as<int>(), S.n_tiles, tile_size,
+                                                S.slots.as<uint32_t>(), n_list, ns, state, aux, S.a_packed.as<float>(),
+                                                S.a_depth.as<float>(), S.counters.as<uint64_t>(), sr);
+            if (rc != RT_OK) return rc;
+            rc = rt_pass_select_tiles_async(scenes[r], p, S.tiles.as<int>(), S.n_tiles, tile_size, state, aux, tol,
+                                            min_samples, S.slots.as<uint32_t>(), S.n_active.as<uint32_t>(), nullptr, sr);
+            if (rc != RT_OK) return rc;
+        }
+        MULTI_HIP(hipMemcpyAsync(g->h_active + r, S.n_active.p, sizeof(uint32_t), hipMemcpyDeviceToHost, sr));
+        MULTI_HIP(hipEventRecord(S.counted, sr));
+        if (d_count)
+            hipLaunchKernelGGL(k_aux_counts, dim3(uint32_t((slots + 255) / 256)), dim3(256), 0, sr, S.aux.as<uint4>(),
+                               uint32_t(slots), S.counts.as<uint32_t>());
+    }
+    const int rc = gather(g, p, tile_size, image, d_rgba, want_depth ? d_depth : nullptr, d_counters, st0, true, d_count);
+    if (rc == RT_OK) g->adaptive = true;
+    return rc;
+}
+
+int rt_group_adaptive_active(rt_group *g, uint32_t *n_active) {
+    if (!g || !n_active || !g->adaptive) return RT_E_ARG;
+    DeviceGuard guard;
+    uint64_t sum = 0;
+    for (int r = 0; r < g->n; r++) {
+        auto &S = *g->share[size_t(r)];
+        if (S.n_tiles == 0) continue;
+        MULTI_HIP(hipSetDevice(g->dev[size_t(r)]));
+        MULTI_HIP(hipEventSynchronize(S.counted));
+        sum += g->h_active[r];
+    }
+    *n_active = uint32_t(std::min<uint64_t>(sum, 0xffffffffu));
+    return RT_OK;
 }
 
 int rt_render_inw_multi(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
@@ -475,6 +647,46 @@ int rt_render_passes_inw_multi(const float *geom, uint32_t n, int layout, const 
                 s0 = cuts[i];
             }
             return int(RT_OK);
+        });
+}
+
+int rt_render_adaptive_inw_multi(const float *geom, uint32_t n, int layout, const float *nodes, const float *lights,
+                                 uint32_t n_lights, const rt_camera *cam, const rt_params *p, const int *devices,
+                                 int n_dev, int tile_size, uint32_t batch, float tol, uint32_t min_samples,
+                                 uint32_t max_rounds, float *rgba, float *depth, uint32_t *count, uint32_t *rounds_out,
+                                 rt_stats *st) {
+    if (!geom || !nodes || n == 0 || !cam || !p || p->width <= 0 || p->height <= 0 || p->spp < 1 ||
+        p->max_bounces < 0 || !rgba || !devices || n_dev <= 0 || (layout != 1 && layout != 4) || tile_size <= 0 ||
+        tile_size % 16 != 0 || batch == 0)
+        return RT_E_ARG;
+    if (layout == 4 && n_lights > 0 && !lights) return RT_E_ARG;
+    if (p->show_normal) return RT_E_UNSUPPORTED;
+    if (st) std::memset(st, 0, sizeof(*st));
+    if (rounds_out) *rounds_out = 0;
+    const size_t npx = size_t(p->width) * size_t(p->height);
+    return inw_multi_blocking(geom, n, layout, nodes, lights, n_lights, p, devices, n_dev, 1, rgba, depth, st,
+        [&](rt_group *g, rt_dev_scene *const *scenes, float *d_rgba, float *d_depth, uint64_t *d_ctr) -> int {
+            Buf d_count;  // on device 0, the current device here
+            if (count) {
+                MULTI_HIP(d_count.ensure(npx * sizeof(uint32_t), devices[0]));
+                MULTI_HIP(hipMemcpy(d_count.p, count, npx * sizeof(uint32_t), hipMemcpyHostToDevice));
+            }
+            // rt_render_adaptive_inw's loop: every pixel listed, then rounds while pixels are active and rounds remain
+            uint32_t n_active = 1, rounds = 0;
+            while (n_active > 0 && (max_rounds == 0 || rounds < max_rounds)) {
+                int rc = rt_render_adaptive_multi_async(g, scenes, cam, p, tile_size, rounds == 0, batch, tol, min_samples,
+                                                        d_rgba, d_depth, d_count.as<uint32_t>(), d_ctr, nullptr);
+                if (rc == RT_OK) rc = rt_group_adaptive_active(g, &n_active);
+                if (rc != RT_OK) return rc;
+                rounds++;
+            }
+            if (count) {
+                MULTI_HIP(hipSetDevice(devices[0]));
+                MULTI_HIP(hipStreamSynchronize(nullptr));
+                MULTI_HIP(hipMemcpy(count, d_count.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            }
+            if (rounds_out) *rounds_out = rounds;
+            return RT_OK;
         });
 }
 

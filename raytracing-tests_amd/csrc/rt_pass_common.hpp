@@ -58,6 +58,30 @@ __device__ __forceinline__ bool listed(const Frame &F, int2 p) {
     return p.x >= 0 && p.y >= 0 && p.x < F.W && p.y < F.H;
 }
 
+// A list entry of the adaptive passes: a pixel of the image, or, on a packed tile list (TL), a slot
+// tile * T * T + iy * T + ix (0xffffffff is rt_pass_select_tiles_async's padding).
+template <bool TL> struct PassEntryOf { using type = int2; };
+template <> struct PassEntryOf<true> { using type = uint32_t; };
+template <bool TL> using PassEntry = typename PassEntryOf<TL>::type;
+constexpr uint32_t kSlotNone = 0xffffffffu;
+
+// A slot entry's pixel: handled (in_image) when the slot is below the list's n_tiles * T * T <= 2^31 and its
+// pixel lies inside the image; out = the slot.  T need not be a power of two.
+__device__ __forceinline__ UnitPix slot_pixel(const Frame &F, uint32_t slot) {
+    UnitPix q;
+    q.x = q.y = -1;
+    q.in_image = false;
+    q.out = slot;
+    const uint32_t T = (uint32_t)F.tile_size, area = T * T;
+    if (slot < (uint32_t)F.n_tiles * area) {
+        const uint32_t t = slot / area, r = slot - t * area, iy = r / T, ix = r - iy * T;
+        q.x = F.tiles[2 * t] * F.tile_size + (int)ix;
+        q.y = F.tiles[2 * t + 1] * F.tile_size + (int)iy;
+        q.in_image = listed(F, make_int2(q.x, q.y));
+    }
+    return q;
+}
+
 // The image of a pixel with k samples folded: acc * RN(1 / k), and the depth.
 __device__ __forceinline__ void pass_write_image(const Frame &F, size_t o, f3 acc, float inv_k, float depth) {
     if (F.out_rgba) {

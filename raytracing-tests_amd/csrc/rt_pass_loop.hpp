@@ -38,24 +38,14 @@ struct UniformPassOf {
 };
 using UniformPass = UniformPassOf<false>;
 
-// Unit u is list entry u; its pixel renders samples [count, min(count + ns, stop)), count = its aux's
-// (aux: even.xyz, the count's bits), folds `even` and leaves even and the new count behind; the image is
-// acc * RN(1 / count).
-struct ListPass {
+// What the two list sources share: an entry's pixel renders samples [count, min(count + ns, stop)), count =
+// its aux's (aux: even.xyz, the count's bits), folds `even` and leaves even and the new count behind; the
+// image is acc * RN(1 / count).  A skipped entry writes nothing.
+struct CountedPass {
     static constexpr bool kEven = true;
-    const int2 *__restrict__ pixels;
     float4 *__restrict__ aux;
     uint32_t stop, ns;
-    __device__ __forceinline__ void frame(Frame &F, const Frame &in) const { pass_frame(F, in); }
     __device__ __forceinline__ void outside(const Frame &, const UnitPix &) const {}
-    __device__ __forceinline__ UnitPix pixel(const Frame &F, uint32_t u) const {
-        const int2 p = pixels[u];
-        UnitPix q;
-        q.x = p.x; q.y = p.y;
-        q.in_image = listed(F, p);
-        q.out = (size_t)((uint32_t)p.y * (uint32_t)F.W + (uint32_t)p.x);
-        return q;
-    }
     __device__ __forceinline__ uint32_t first(size_t out, f3 &ev) const {
         const float4 x = aux[out];
         ev = f3{x.x, x.y, x.z};
@@ -69,6 +59,33 @@ struct ListPass {
     __device__ __forceinline__ void keep(size_t out, f3 ev, uint32_t s) const {
         aux[out] = make_float4(ev.x, ev.y, ev.z, __uint_as_float(s));
     }
+};
+
+// Unit u is list entry u, a pixel of the image; state, aux and image are indexed by y * W + x.
+struct ListPass : CountedPass {
+    const int2 *__restrict__ pixels;
+    __device__ ListPass(const int2 *px, float4 *aux_, uint32_t stop_, uint32_t ns_)
+        : CountedPass{aux_, stop_, ns_}, pixels(px) {}
+    __device__ __forceinline__ void frame(Frame &F, const Frame &in) const { pass_frame(F, in); }
+    __device__ __forceinline__ UnitPix pixel(const Frame &F, uint32_t u) const {
+        const int2 p = pixels[u];
+        UnitPix q;
+        q.x = p.x; q.y = p.y;
+        q.in_image = listed(F, p);
+        q.out = (size_t)((uint32_t)p.y * (uint32_t)F.W + (uint32_t)p.x);
+        return q;
+    }
+};
+
+// The same on a packed tile list (rt_render_pass_slots_async): unit u is slot entry u (slot_pixel), and state,
+// aux and image are indexed by slot.  The zero image of the slots outside the image stays the uniform tile
+// pass's business.
+struct SlotPass : CountedPass {
+    const uint32_t *__restrict__ slots;
+    __device__ SlotPass(const uint32_t *sl, float4 *aux_, uint32_t stop_, uint32_t ns_)
+        : CountedPass{aux_, stop_, ns_}, slots(sl) {}
+    __device__ __forceinline__ void frame(Frame &F, const Frame &in) const { pass_frame_tiles(F, in); }
+    __device__ __forceinline__ UnitPix pixel(const Frame &F, uint32_t u) const { return slot_pixel(F, slots[u]); }
 };
 
 // state: 2 float4 per pixel of the image (rt_pass_state: the sum | the RI fields of the four ray-stack
@@ -99,7 +116,7 @@ __device__ __forceinline__ void iow_pass_loop(const Frame &Fin, const IowScene &
     bool drained = false;        // the queue is empty (wave-uniform)
     bool busy = false;           // the lane owns a pixel: samples [s, s1) are left
     bool walking = false;        // ... and sample s's path is under way
-    uint32_t s = 0, s1 = 0, out = 0;  // out = y * W + x < 2^31
+    uint32_t s = 0, s1 = 0, out = 0;  // out = y * W + x, or the slot, < 2^31
     int skip = 0;
     float sx = 0.0f, sy = 0.0f;
     f3 fc = f3{0, 0, 0}, ev = f3{0, 0, 0}, col = f3{0, 0, 0};

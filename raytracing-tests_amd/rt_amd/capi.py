@@ -276,6 +276,20 @@ SIGNATURES = {
     "rt_render_passes_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
                                              C.POINTER(RtParams), _IP, C.c_int, C.c_int, _U32P, C.c_int, _FP, _FP,
                                              C.POINTER(RtStats)]),
+    "rt_render_pass_slots_async": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_void_p,
+                                             C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_pass_select_tiles_async": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "rt_render_adaptive_multi_async": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtParams),
+                                                 C.c_int, C.c_int, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_group_adaptive_active": (C.c_int, [C.c_void_p, _U32P]),
+    "rt_render_adaptive_inw_multi": (C.c_int, [_FP, C.c_uint32, C.c_int, _FP, _FP, C.c_uint32, C.POINTER(RtCamera),
+                                               C.POINTER(RtParams), _IP, C.c_int, C.c_int, C.c_uint32, C.c_float,
+                                               C.c_uint32, C.c_uint32, _FP, _FP, C.c_void_p, C.c_void_p,
+                                               C.POINTER(RtStats)]),
 }
 
 _lib = None
@@ -1016,7 +1030,8 @@ PASS_TILE_KERNELS = {16: "k_pass_rays tile list (INW)", 17: "k_pass_fold tile li
 
 def pass_kernel_info(which: int) -> dict:
     """rt_debug_pass_kernel: registers, scratch, LDS and resident blocks per CU of PASS_KERNELS[which]
-    (which = 0..3), ADAPTIVE_KERNELS[which] (8..14) or PASS_TILE_KERNELS[which] (16..19)."""
+    (which = 0..3), ADAPTIVE_KERNELS[which] (8..14), PASS_TILE_KERNELS[which] (16..19) or
+    ADAPTIVE_TILE_KERNELS[which] (24..28, 30)."""
     info = (C.c_int * 4)()
     check(load().rt_debug_pass_kernel(int(which), info), "rt_debug_pass_kernel")
     return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
@@ -1029,6 +1044,14 @@ PIXEL_DTYPE = np.dtype([("x", np.int32), ("y", np.int32)])
 # rt_debug_pass_kernel's `which` of the adaptive-pass kernels
 ADAPTIVE_KERNELS = {8: "k_adapt_rays (INW)", 9: "k_adapt_fold (INW)", 10: "k_iow_adapt LDS nodes",
                     11: "k_iow_adapt global nodes", 12: "k_select_count", 13: "k_select_scan", 14: "k_select_scatter"}
+
+
+# ... and of their tile-list instances (rt_render_pass_slots_async, rt_pass_select_tiles_async): + 16; the scan
+# serves both forms
+ADAPTIVE_TILE_KERNELS = {24: "k_adapt_rays tile list (INW)", 25: "k_adapt_fold tile list (INW)",
+                         26: "k_iow_adapt tile list, LDS nodes", 27: "k_iow_adapt tile list, global nodes",
+                         28: "k_select_count tile list", 30: "k_select_scatter tile list"}
+SLOT_NONE = 0xFFFFFFFF  # RT_SLOT_NONE: the padding of a slot list
 
 
 def _dptr(t):
@@ -1106,6 +1129,62 @@ def pass_select(handle, params: RtParams, d_state, d_aux, tol: float, min_sample
     """rt_pass_select_async on device buffers (pointers or torch tensors); returns the status."""
     return load().rt_pass_select_async(handle, C.byref(params), _dptr(d_state), _dptr(d_aux), float(tol),
                                        int(min_samples), _dptr(d_list), _dptr(d_n_active), _dptr(d_err), stream)
+
+
+def pass_slots(handle, camera: RtCamera, params: RtParams, d_tiles, n_tiles: int, tile_size: int, d_slots,
+               n_slots: int, ns: int, d_state, d_aux, d_out=None, d_depth=None, d_counters=None, stream=None) -> int:
+    """rt_render_pass_slots_async on device buffers (pointers or torch tensors); returns the status."""
+    return load().rt_render_pass_slots_async(handle, C.byref(camera), C.byref(params), _dptr(d_tiles), n_tiles,
+                                             tile_size, _dptr(d_slots), n_slots, ns, _dptr(d_state), _dptr(d_aux),
+                                             _dptr(d_out), _dptr(d_depth), _dptr(d_counters), stream)
+
+
+def pass_select_tiles(handle, params: RtParams, d_tiles, n_tiles: int, tile_size: int, d_state, d_aux, tol: float,
+                      min_samples: int, d_slots, d_n_active, d_err=None, stream=None) -> int:
+    """rt_pass_select_tiles_async on device buffers (pointers or torch tensors); returns the status."""
+    return load().rt_pass_select_tiles_async(handle, C.byref(params), _dptr(d_tiles), n_tiles, tile_size,
+                                             _dptr(d_state), _dptr(d_aux), float(tol), int(min_samples),
+                                             _dptr(d_slots), _dptr(d_n_active), _dptr(d_err), stream)
+
+
+def render_adaptive_multi_round(group, scenes, camera: RtCamera, params: RtParams, tile: int, first: bool, ns: int,
+                                tol: float, min_samples: int, d_rgba=None, d_depth=None, d_count=None,
+                                d_counters=None, stream=None) -> int:
+    """rt_render_adaptive_multi_async: one adaptive round of the group (scenes: a ctypes array of one device
+    scene per group device; the buffers are device-0 pointers or torch tensors); returns the status."""
+    return load().rt_render_adaptive_multi_async(group, scenes, C.byref(camera), C.byref(params), tile,
+                                                 1 if first else 0, ns, float(tol), int(min_samples), _dptr(d_rgba),
+                                                 _dptr(d_depth), _dptr(d_count), _dptr(d_counters), stream)
+
+
+def group_adaptive_active(group) -> int:
+    """rt_group_adaptive_active: the active slots the group's last adaptive round left (waits for the counts)."""
+    n = C.c_uint32(0)
+    check(load().rt_group_adaptive_active(group, C.byref(n)), "rt_group_adaptive_active")
+    return int(n.value)
+
+
+def render_adaptive_multi(sc: Scene, devices, batch: int, tol: float, min_samples: int = 2,
+                          max_rounds: int | None = None, tile: int = 16, rgba=None, depth=None) -> dict:
+    """rt_render_adaptive_inw_multi: the blocking adaptive loop of the INW frame (sc.camera, sc.params) on the
+    device group `devices`.  Returns {"rgba": (H, W, 4), "depth": (H, W), "count": (H, W) uint32, "rounds":
+    int, "stats": dict}; rgba and depth: arrays of those shapes to start from, default zeros."""
+    p = sc.params
+    H, W = p.height, p.width
+    rgba = np.zeros((H, W, 4), np.float32) if rgba is None else np.ascontiguousarray(rgba, np.float32)
+    depth = np.zeros((H, W), np.float32) if depth is None else np.ascontiguousarray(depth, np.float32)
+    assert rgba.shape == (H, W, 4) and depth.shape == (H, W)
+    count = np.zeros((H, W), np.uint32)
+    rounds = C.c_uint32(0)
+    devs = (C.c_int * len(devices))(*devices)
+    lights = sc.lights if sc.lights is not None and len(sc.lights) else None
+    st = RtStats()
+    check(load().rt_render_adaptive_inw_multi(fptr(sc.geom), sc.n, sc.layout, fptr(sc.nodes), fptr(lights), sc.n_lights,
+                                              C.byref(sc.camera), C.byref(p), devs, len(devices), tile, int(batch),
+                                              float(tol), int(min_samples), int(max_rounds or 0), fptr(rgba),
+                                              fptr(depth), count.ctypes.data, C.addressof(rounds), C.byref(st)),
+          "rt_render_adaptive_inw_multi")
+    return {"rgba": rgba, "depth": depth, "count": count, "rounds": int(rounds.value), "stats": st.as_dict()}
 
 
 def render_adaptive(sc: Scene, batch: int, tol: float, min_samples: int = 2, max_rounds: int | None = None,
