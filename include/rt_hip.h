@@ -436,7 +436,7 @@ int rt_render_image_async(rt_dev_scene *s, const rt_camera *cam, const rt_params
  * shader's closest-hit walk leaves behind -- layout 1: 01_BoundingVolumeHierarchy/
  * computeShaderSrc.glsl:431-473 with IntersectRay :230-269; layout 4: 04_Lights_Camera_And_Action/
  * computeShaderSrc.glsl:524-563 -- started on an EMPTY 40-float stack with t_limiting = tmax, the
- * object positions of time ratio `ratio` (0..1, the shader's sample index / samples), and the child
+ * object positions of time ratio `ratio` (the shader's sample index / samples, 0..1 there), and the child
  * order RT_TRACE_INVERT selects (set: the order the shader takes when dot(u_Camera.Direction,
  * (1,1,1)) > 0).  The kernel runs the render path's own walk (the scene's options apply: wide
  * walk, time-bin trees, sphere records, compact nodes, stackless walks, fused cull), so results
@@ -452,6 +452,10 @@ int rt_render_image_async(rt_dev_scene *s, const rt_camera *cam, const rt_params
  *   - tmax <= 0 or NaN: a miss by the shader's own tests (t > 0 && t < t_limiting); no walk runs.
  *   - A direction with zero or non-finite components gives what the reference walk gives (its
  *     reciprocals are infinite or NaN; the box tests then follow IEEE min / max).
+ *   - Any ratio is answered as the shader would: its object positions are position - delta *
+ *     (1 - ratio) whatever the ratio, below 0, above 1, infinite or NaN.  A ratio outside [0, 1]
+ *     (or NaN) takes the reference walk: the time-bin trees and the swept boxes cover [0, 1] only.
+ *   - So does an origin farther than 1000 from the world origin on some axis, NaN included.
  *   - RT_TRACE_ANY (occlusion): id >= 0 exactly when the closest-hit query hits; id is then some
  *     accepted object and t its t, t_closest <= t < tmax; n = 0 and extra = 0.
  *   - counters (6 x u64 as rt_stats' first six fields, added to): [0] += n_rays; [1], [2] the node
@@ -528,6 +532,9 @@ int rt_trace_iow03(const float *types, const float *records /* N*24 */, uint32_t
  *     scatter offsets are sunflower[2s], [2s + 1] of the scene's table; spp is the value the scene
  *     was created with.  u_NumOfBounces = max_bounces.  pad is ignored: any bits may be in it.
  *   - The primary ray's limit is the shader's 32000; there is no per-ray tmax.
+ *   - A query whose origin lies farther than 1000 from the world origin on some axis (NaN included)
+ *     runs its whole path on the reference walks, with or without the fused cull: the same answer,
+ *     without the culling trees.
  *   - RT_TRACE_INVERT selects the child order of the walks, as for rt_trace_rays_async.  Any other
  *     flag bit is an error.
  *   - rgb = the loop's final `color`: before End()'s sqrt, and (1, 1, 1) after INW-04's

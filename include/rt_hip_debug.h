@@ -134,6 +134,10 @@ int rt_debug_kernel_time(rt_dev_scene *s, double *ms_total, int *launches);
  * depth-first ranks (invert 0, then 1) when the wide walk is built.  Lets the tests compare the
  * device build (rt_dev_scene_inw_update) with the host build of a fresh scene. */
 int rt_debug_wide_info(rt_dev_scene *s, uint32_t info[8], uint32_t *rank_out);
+/* 1 when the scene's ray, path and pixel queries and passes launch the fused-cull instance of their
+ * kernel (rt_options.inw_fused_cull, a wide tree, every culling box within 1000 of the origin), else 0;
+ * RT_E_ARG for a null or IOW-03 scene.  The decision the launches themselves take. */
+int rt_debug_query_fused(rt_dev_scene *s);
 /* Test hook: the device build of the walk structures (rt_dev_scene_inw_update) and of the IOW-03
  * culling BVH (rt_dev_scene_iow03_update) launches at most `levels` SAH / collapse levels (0 = its own
  * cap, 256); a deeper tree is built on the host instead (rt_debug_wide_info info[7] = 2,

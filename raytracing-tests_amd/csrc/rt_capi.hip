@@ -377,6 +377,12 @@ extern "C" {
 
 int rt_abi_version(void) { return RT_ABI_VERSION; }
 
+// rt_hip_debug.h: the fused-cull decision of the query and pass launches (inw_query_view's)
+int rt_debug_query_fused(rt_dev_scene *s) {
+    if (!s || s->kind == 3) return RT_E_ARG;
+    return inw_query_view(s).fused;
+}
+
 void rt_options_default(rt_options *o) {
     if (o) *o = default_options();
 }

@@ -28,7 +28,9 @@ constexpr int kPathWaves = 3;
 // within 1000 of the world origin on every axis.  Bounce origins lie on objects inside the scene's
 // boxes (the host checks those); a path whose query origin is farther out runs with dfs_high past
 // the stack, the walks' own "a push could drop" condition, which sends all of it to the
-// reference's walks (as k_inw_trace does per query).
+// reference's walks (as k_inw_trace does per query).  The origin test holds without the fused cull
+// too: thousands of units from the objects the object test's t falls below the hit's own box entry,
+// which the wide walk's cut at t * 1.0001 + 1e-3 assumes it never does (rt_trace.hip).
 template <bool LIGHTS, bool FU>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPathWaves)))
 void k_inw_paths(InwScene S, const float4 *__restrict__ rays, uint32_t n_rays, uint32_t spp, int max_bounces,
@@ -76,7 +78,7 @@ void k_inw_paths(InwScene S, const float4 *__restrict__ rays, uint32_t n_rays, u
                 } else {
                     const f3 o = mk(r0.x, r0.y, r0.z), d = mk(r1.x, r1.y, r1.z);
                     dfs_high = S.dfs_high;
-                    if (FU && !(fabsf(o.x) <= 1000.0f && fabsf(o.y) <= 1000.0f && fabsf(o.z) <= 1000.0f))
+                    if (!(fabsf(o.x) <= 1000.0f && fabsf(o.y) <= 1000.0f && fabsf(o.z) <= 1000.0f))
                         dfs_high = (uint32_t)kFStack + 1u;
                     s = (int)sample;
                     K.reset(0);

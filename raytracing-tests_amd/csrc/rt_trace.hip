@@ -19,6 +19,11 @@ namespace rtk {
 // the scene's boxes, the kernel each query's origin: a lane whose origin is farther out runs with
 // dfs_high past the stack, which is the walks' own "a push could drop" condition, so inw_closest
 // hands it to the reference's stack walk.
+// The origin test holds without the fused cull too.  The wide walk stops at t * 1.0001 + 1e-3 because a
+// hit lies no nearer than its box entry; from 10^6 away the object test's t is off by hundreds (the
+// quadratic cancels) while the box entry is not, t < entry for every hit, and the reference -- which
+// then keeps the first hit its depth-first order reaches -- and the near-to-far walk answered
+// differently (tests/test_gpu_query_edges.py, class org_1e6).
 template <bool ANY, bool FU>
 __global__ __launch_bounds__(kBlock) void k_inw_trace(InwScene S, const float4 *__restrict__ rays, uint32_t n_rays,
                                                       uint32_t invert, float4 *__restrict__ hits,
@@ -42,8 +47,11 @@ __global__ __launch_bounds__(kBlock) void k_inw_trace(InwScene S, const float4 *
             c.seg++;
             if (tmax > 0.0f) {  // else (or NaN) a miss by the shader's tests: t > 0 && t < t_limiting never holds
                 InwScene Sq = S;
-                if (FU && !(fabsf(o.x) <= 1000.0f && fabsf(o.y) <= 1000.0f && fabsf(o.z) <= 1000.0f))
+                if (!(fabsf(o.x) <= 1000.0f && fabsf(o.y) <= 1000.0f && fabsf(o.z) <= 1000.0f))
                     Sq.dfs_high = (uint32_t)kFStack + 1u;
+                // the time ratio is the caller's: the time-bin trees (and the swept tree's boxes) cover
+                // ratios 0..1 only, and the bin index of any other ratio (or NaN) names no tree
+                if (!(ratio >= 0.0f && ratio <= 1.0f)) Sq.dfs_high = (uint32_t)kFStack + 1u;
                 K.size = 0;
                 g = inw_closest<!ANY, false, FU>(Sq, K, o, d, ratio, invert != 0u, tlim, n, extra, -1.0f, c);
             }

@@ -196,6 +196,7 @@ SIGNATURES = {
     "rt_beam_keep_host": (C.c_int, [_FP, _FP, C.c_float, C.c_float, C.c_float, C.c_float, _FP, _FP, C.c_uint32,
                                     C.c_uint32, C.c_int, _IP]),
     "rt_debug_wide_info": (C.c_int, [C.c_void_p, _U32P, _U32P]),
+    "rt_debug_query_fused": (C.c_int, [C.c_void_p]),
     "rt_tile_deal": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _IP, C.c_int]),
     "rt_group_create": (C.c_void_p, [_IP, C.c_int]),
     "rt_debug_build_level_cap": (C.c_int, [C.c_int]),

@@ -206,9 +206,14 @@ def test_a_frame_is_the_fold_of_its_path_queries(gpu, name):
         assert pst[k] == st[k], k
 
 
-def test_far_origins_agree_with_the_reference_walk(gpu):
+@pytest.fixture(scope="module")
+def ref_lib(tmp_path_factory):
+    return P.build(tmp_path_factory.mktemp("path_ref"))
+
+
+def test_far_origins_agree_with_the_reference_walk(gpu, ref_lib):
     """Query origins beyond the fused cull's bound (1000 from the world origin) send their whole path
-    to the reference walks: the same bytes as a scene built without the wide walk."""
+    to the reference walks: the same bytes as a scene built without the wide walk, and as the oracle's loop."""
     f = fx("mixed300")
     rays = f.rays[:512].copy()
     length = np.linalg.norm(rays["d"].astype(np.float64), axis=1, keepdims=True)
@@ -219,6 +224,11 @@ def test_far_origins_agree_with_the_reference_walk(gpu):
         ref, _ = R.paths(f, rays, f.max_bounces)
     assert_same(out, ref, "far origins")
     assert 0.0 < (out["segments"] > 1).mean() < 1.0
+    for invert in (0, 1):
+        want, wctr = P.run(ref_lib, f, rays, invert)
+        out, st = R.paths(f, rays, f.max_bounces, invert * R.RT_TRACE_INVERT)
+        assert_same(out, want, f"far origins against the oracle, invert {invert}")
+        assert_ref_counters(stats_list(st), wctr, f"far origins against the oracle, invert {invert}")
 
 
 def test_invalid_samples(gpu):
@@ -278,7 +288,7 @@ def test_null_counters(gpu):
 def test_kernel_resources(gpu):
     """The path kernel as loaded: the 40-float stacks of 256 lanes in LDS, and the registers and
     (no) scratch of DESIGN.md 5.9's table at three waves per SIMD."""
-    table = {(False, False): 141, (False, True): 142, (True, False): 162, (True, True): 162}
+    table = {(False, False): 142, (False, True): 142, (True, False): 162, (True, True): 162}
     for (lights, fused), vgprs in table.items():
         info = R.paths_kernel_info(lights, fused)
         print("k_inw_paths", "lights" if lights else "inw01", "fused" if fused else "plain", info)

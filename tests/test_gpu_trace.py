@@ -196,9 +196,14 @@ def test_limits_that_cannot_hit(gpu):
     assert st["segments"] == 64 and st["stack_drops"] == 0
 
 
-def test_far_origins_agree_with_the_reference_walk(gpu):
+@pytest.fixture(scope="module")
+def ref_lib(tmp_path_factory):
+    return T.build(tmp_path_factory.mktemp("trace_ref"))
+
+
+def test_far_origins_agree_with_the_reference_walk(gpu, ref_lib):
     """Origins beyond the fused cull's bound (1000 from the world origin) take the reference walk:
-    the same answers as a scene built without the wide walk."""
+    the same answers as a scene built without the wide walk, and as the oracle's walk."""
     f = fx("mixed700")
     rays = f.rays[:512].copy()
     length = np.linalg.norm(rays["d"].astype(np.float64), axis=1, keepdims=True)
@@ -209,6 +214,11 @@ def test_far_origins_agree_with_the_reference_walk(gpu):
         ref, _ = R.trace(f, rays)
     assert_same(hits, ref, "far origins")
     assert 0.2 < (hits["id"] >= 0).mean() < 1.0
+    for invert in (0, 1):
+        want, ctr = T.run(ref_lib, f.geom, f.nodes, f.layout, rays, invert)
+        hits, st = R.trace(f, rays, invert * R.RT_TRACE_INVERT)
+        assert_same(hits, want, f"far origins against the oracle, invert {invert}")
+        assert st["segments"] == len(rays) and st["stack_drops"] == int(ctr[2])
 
 
 def test_errors_on_a_device(gpu):
