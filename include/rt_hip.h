@@ -415,6 +415,42 @@ int rt_inw_swept_boxes_async(const float *d_geom, uint32_t n, float *d_aabbs_out
 #define RT_UPDATE_DEVICE_BUILD 2   /* culling BVH built on the device */
 int rt_dev_scene_iow03_update(rt_dev_scene *s, const float *types, const float *records /* N*24 */,
                               uint32_t n, int flags, double timing_ms[4]);
+/* rt_dev_scene_iow03_update for types and records that live on the scene's device: the edit loop of a
+ * host that changes the scene on the GPU (a torch optimiser or simulation that keeps the n*24 records
+ * in device memory) runs device to device, records -> update -> frame.  d_types: n; d_records: n*24,
+ * read fastest when 16-byte aligned, correct at any 4-byte alignment.  n may stay, grow or shrink;
+ * spp, the sample tables, the workspaces and the speculation records are kept, and so are the scene's
+ * [build] options (a scene created with iow_linear = 1 builds no BVH; n < 2 or n >= 16384 means no
+ * BVH).
+ * The inputs are read in `stream` order (a producer kernel enqueued on `stream` before the call needs no
+ * synchronisation) and all device work runs on `stream`.  The call synchronises the device first, as
+ * rt_dev_scene_iow03_update does, and `stream` at the end (the build reads its counts back): when it
+ * returns, a render or query on any stream, a non-blocking one included, may follow at once.
+ * The hot and cold records come from a kernel (byte-equal to the host packer's: IEEE division for the
+ * 1/scale values, the identity flag from the rotation's bit patterns), the RI priors from a sort of
+ * the RI values on the device and a run-length pass (the host's answers for every scene whose RIs hold
+ * no NaN and no -0.0; ten words of result are all that is read back).  After the call the scene
+ * behaves as rt_dev_scene_iow03(types, records, n, spp) with the same options would: bit for bit for
+ * every render and query rt_dev_scene_iow03_update lists, and for rt_render_pass_async,
+ * rt_render_pass_pixels_async and their tile-list forms.  Counters [0], [4] and [5] are the fresh
+ * scene's; [1] and [2] are the build's own.
+ * flags: the two bits of rt_dev_scene_iow03_update; both together, or any other bit, is RT_E_ARG.
+ * RT_UPDATE_DEVICE_BUILD: no record byte crosses to the host.  RT_UPDATE_HOST_BUILD: the types and
+ * records are copied back once (n*25 floats) and rtamd::iow_cull_build runs as for a fresh scene; the
+ * hot and cold records and the priors still come from the device kernels.  0 is the library's choice by
+ * the same rule and the same constant as rt_dev_scene_iow03_update: the device build from 1024 objects
+ * on, below that the host build with the one copy-back (under 100 KB) -- because at 486 objects the
+ * device's binned tree slowed the C2 frame by 2.1%, far more than the copy costs
+ * (DESIGN.md §5.18).  A device build that runs past its level cap, or meets a box that is not
+ * finite, is redone by the host builder after the same copy-back (rt_debug_iow_info info[3] = 2 or 3).
+ * timing_ms (may be NULL) receives the host time of {records and priors (their enqueue); boxes and
+ * culling BVH; copy-back plus upload of host-built structures, 0 for the device build; the whole call}.
+ * RT_E_ARG for a null scene, null d_types or d_records, n == 0 or bad flags, and RT_E_UNSUPPORTED for an
+ * INW scene, come back before a device is touched, the scene untouched and still valid, timing_ms
+ * unwritten.  A later failure leaves the scene broken as rt_dev_scene_iow03_update does. */
+int rt_dev_scene_iow03_update_device(rt_dev_scene *s, const float *d_types /* n, device */,
+                                     const float *d_records /* n*24, device */, uint32_t n,
+                                     int flags, void *stream, double timing_ms[4]);
 /* Replace the scene's options (the [build] ones keep the values the scene was built with). */
 int rt_dev_scene_set_options(rt_dev_scene *s, const rt_options *o);
 

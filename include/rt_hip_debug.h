@@ -207,6 +207,21 @@ int rt_debug_iow_info(rt_dev_scene *s, uint32_t info[8]);
  * layout of rt_debug_iow_host_dump: info = {wide nodes (0: linear loop), 0, 0, 0}; wide and obox may
  * be NULL.  (rt_debug_walk_dump keeps refusing IOW-03 scenes.) */
 int rt_debug_iow_dump(rt_dev_scene *s, uint32_t info[4], float *wide, float *obox);
+/* The IOW-03 record packer and RI priors as rt_dev_scene_iow03 runs them on the host, no device: hot (n *
+ * 20 floats: pos3 type M9 scale3 1/scale3 identity flag), cold (n * 8: colour3 material3 scat2) and
+ * priors = {ri_prior (the most common RefractiveIndex, record float 20; the smallest among equals),
+ * alt_vals[8] (the ascending distinct bit patterns of {0, 1} and the RIs when there are at most 8; 0
+ * past the count), n_alt_vals as a float}.  Each output may be NULL.  RT_E_ARG for null inputs or
+ * n == 0.  What rt_dev_scene_iow03_update_device's kernels must reproduce byte for byte. */
+int rt_debug_iow_prepare_host(const float *types, const float *records, uint32_t n, float *hot, float *cold,
+                              float priors[10]);
+/* The scene's current hot records, cold records and priors in the same layouts (synchronises; each
+ * output may be NULL).  RT_E_ARG for a null, INW or broken scene. */
+int rt_debug_iow_records(rt_dev_scene *s, float *hot, float *cold, float priors[10]);
+/* {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of the kernels of
+ * rt_dev_scene_iow03_update_device: k_iow_prepare with float4 loads (which = 0) and with scalar loads
+ * (1), k_iow_mode (2), k_iow_priors (3; one 64-lane block).  Needs a device. */
+int rt_debug_update_iow_kernel(int which, int info[4]);
 /* The ray-query kernel (rt_trace_rays_async) as the loaded code object has it: info = {VGPRs,
  * scratch bytes per lane, static LDS bytes per block, resident 256-lane blocks per CU} of the
  * closest-hit (any = 0) or RT_TRACE_ANY instance, with the fused cull or without.  Needs a device. */

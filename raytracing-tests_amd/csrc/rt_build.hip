@@ -15,6 +15,9 @@
 // runs of the same SAH levels and collapse over k_bin_boxes' boxes, laid out by k_bin_place.
 // The same SAH levels and collapse build the IOW-03 culling BVH of a scene update
 // (iow_cull_build_device) over boxes made from the hot records (k_iow_boxes).
+// An IOW-03 update from device-resident records (rt_dev_scene_iow03_update_device) makes
+// those hot records, the cold records and the RI priors here too (k_iow_prepare, k_iow_mode,
+// k_iow_priors around a radix sort of the RI keys).
 // The host path (rtamd::inw_wide_build: a full-sweep SAH) stays for fresh scenes; binned with 32
 // bins its SAH cost over the C3 leaf boxes is within 0.3% of the sweep's (16.80 against 16.75).
 // Every structure is a culling or bookkeeping structure: the walks' results do not depend on
@@ -595,6 +598,104 @@ __global__ __launch_bounds__(kB) void k_iow_boxes(const float *hot, uint32_t n, 
     if (!fin) atomicOr(meta, 1u);
 }
 
+// ---- IOW-03 update from device-resident records (rt_dev_scene_iow03_update_device)
+// The hot and cold records of every object by the statements of iow_records (rt_scene_build.hip): plain
+// copies, the three 1 / scale as the correctly rounded divide, the identity flag from the rotation's
+// bit patterns (glm::mat3(1): a -0.0 off the diagonal is not the identity), pad floats zero -- so the
+// bytes equal the host's.  keys: the orderable bits of the RI (record float 20) for the priors' sort.
+// One lane per object, no LDS; VEC: rec is 16-byte aligned (a record is 96 bytes: six float4 loads).
+template <bool VEC>
+__global__ __launch_bounds__(kB) void k_iow_prepare(const float *types, const float *rec, uint32_t n, float4 *hot,
+                                                    float4 *cold, uint32_t *keys) {
+    const uint32_t j = blockIdx.x * kB + threadIdx.x;
+    if (j >= n) return;  // no cross-lane work in this kernel
+    float r[24];
+    if constexpr (VEC) {
+        const float4 *src = reinterpret_cast<const float4 *>(rec) + (size_t)j * 6;
+        for (int k = 0; k < 6; k++) {
+            const float4 v = src[k];
+            r[4 * k] = v.x; r[4 * k + 1] = v.y; r[4 * k + 2] = v.z; r[4 * k + 3] = v.w;
+        }
+    } else {
+        const float *src = rec + (size_t)j * 24;
+        for (int k = 0; k < 24; k++) r[k] = src[k];
+    }
+    bool ident = true;
+    for (int k = 0; k < 9; k++) ident = ident && __float_as_uint(r[3 + k]) == ((k % 4) == 0 ? 0x3f800000u : 0u);
+    float4 *h = hot + (size_t)j * (kIowHot / 4);
+    h[0] = make_float4(r[0], r[1], r[2], types[j]);
+    h[1] = make_float4(r[3], r[4], r[5], r[6]);
+    h[2] = make_float4(r[7], r[8], r[9], r[10]);
+    h[3] = make_float4(r[11], r[12], r[13], r[14]);
+    h[4] = make_float4(1.0f / r[12], 1.0f / r[13], 1.0f / r[14], ident ? 1.0f : 0.0f);
+    float4 *c = cold + (size_t)j * (kIowCold / 4);
+    c[0] = make_float4(r[15], r[16], r[17], r[18]);
+    c[1] = make_float4(r[19], r[20], r[21], r[22]);
+    keys[j] = ford(r[20]);
+}
+
+// The RI priors (iow_priors, rt_scene_build.hip) from the sorted keys.  Runs are compared by == as the
+// host compares them, so -0.0 joins +0.0's run (their keys are neighbours); the distinct values are bit
+// patterns, i.e. distinct keys.  NaNs order by their bits here: outside the priors' contract (the host's
+// std::sort has none for them), but every search below ends and stays inside [0, n).
+constexpr uint32_t kKeyZero = 0x80000000u, kKeyNegZero = 0x7fffffffu, kKeyOne = 0xbf800000u;  // ford(0.0f), (-0.0f), (1.0f)
+__device__ __forceinline__ uint32_t ri_class(uint32_t key) { return key == kKeyNegZero ? kKeyZero : key; }
+// the first index in (lo, n) whose key (CLS: whose == class) is above keys[lo]'s, or n
+template <bool CLS>
+__device__ __forceinline__ uint32_t run_end(const uint32_t *keys, uint32_t n, uint32_t lo) {
+    const uint32_t k0 = CLS ? ri_class(keys[lo]) : keys[lo];
+    uint32_t a = lo + 1u, b = n;  // keys[lo .. a) are not above k0, keys[b .. n) are
+    while (a < b) {
+        const uint32_t m = a + (b - a) / 2u;
+        const uint32_t km = CLS ? ri_class(keys[m]) : keys[m];
+        if (km > k0) b = m;
+        else a = m + 1u;
+    }
+    return a;
+}
+// The mode: every lane at the head of a run finds the run's end by bisection; (length, ~key of the head)
+// orders as the host's scan picks (the longest run, the smallest value among equals); a wave folds its
+// lanes, one atomic per wave.  best: zeroed by the launcher.
+__global__ __launch_bounds__(kB) void k_iow_mode(const uint32_t *keys, uint32_t n, unsigned long long *best) {
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    unsigned long long v = 0ull;
+    if (i < n && (i == 0u || ri_class(keys[i - 1u]) != ri_class(keys[i])))
+        v = ((unsigned long long)(run_end<true>(keys, n, i) - i) << 32) | (unsigned long long)(~keys[i]);
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = (unsigned long long)__shfl_xor((long long)v, off, 64);
+        v = o > v ? o : v;
+    }
+    if ((threadIdx.x & 63u) == 0u && v) atomicMax(best, v);
+}
+// The ten result words {ri_prior, alt_vals[8], n_alt_vals as a float}: the mode decoded, and the ascending
+// distinct bit patterns of {0.0f, 1.0f} and the RIs when there are at most 8 (else none, all zero): at
+// most 9 bisections by one lane, the list kept in LDS (indexed at run time).
+__global__ __launch_bounds__(64) void k_iow_priors(const uint32_t *keys, uint32_t n, const unsigned long long *best,
+                                                   uint32_t *out) {
+    __shared__ uint32_t s_v[8];
+    if (threadIdx.x != 0u) return;
+    uint32_t nd = 0u;
+    bool over = false;
+    for (uint32_t pos = 0u; pos < n; pos = run_end<false>(keys, n, pos)) {
+        if (nd == 8u) { over = true; break; }
+        s_v[nd++] = keys[pos];
+    }
+    for (int e = 0; e < 2 && !over; e++) {  // 0.0f and 1.0f join the list where they are not in it
+        const uint32_t k = e ? kKeyOne : kKeyZero;
+        uint32_t p = 0u;
+        while (p < nd && s_v[p] < k) p++;
+        if (p < nd && s_v[p] == k) continue;
+        if (nd == 8u) { over = true; break; }
+        for (uint32_t q = nd; q > p; q--) s_v[q] = s_v[q - 1u];
+        s_v[p] = k;
+        nd++;
+    }
+    if (over) nd = 0u;
+    out[0] = __float_as_uint(fdeo(~(uint32_t)(*best & 0xffffffffull)));
+    for (uint32_t v = 0u; v < 8u; v++) out[1u + v] = v < nd ? __float_as_uint(fdeo(s_v[v])) : 0u;
+    out[9] = __float_as_uint((float)nd);
+}
+
 // ---- surrounding-RI grid (rtamd::ri_grid_build): bounds, per-cell counts, offsets, ids
 __global__ __launch_bounds__(kB) void k_ri_bounds(const float4 *leafbox, uint32_t n, uint32_t *bnd) {
     const uint32_t g = blockIdx.x * kB + threadIdx.x;
@@ -782,10 +883,12 @@ size_t inw_build_workspace_bytes(uint32_t n) { return n ? carve(reinterpret_cast
 // launch per level) and its 4-wide collapse into wnodes (NF4 float4 per node, one k_collapse_level
 // launch per level).  The pending-task counts are read back every few levels; the last read brings
 // the counters (meta: [0] the caller's flag word, [1] wide nodes, [2], [3] the INW walk's high-water
-// mark and wbound) and w.ri_bnd along.  hipErrorNotSupported: deeper than lvl_cap.
+// mark and wbound, [4..13] the ten words a caller placed there after build_begin: the IOW-03 priors)
+// and w.ri_bnd along.  hipErrorNotSupported: deeper than lvl_cap.
+constexpr int kMetaRead = 14;
 struct BuildLevels {
     int depth;
-    uint32_t meta[4], bnd[6];
+    uint32_t meta[kMetaRead], bnd[6];
 };
 static int level_cap(int max_levels) { return max_levels > 0 && max_levels < kMaxLevels ? max_levels : kMaxLevels; }
 static hipError_t build_begin(const BuildWs &w, hipStream_t s) {
@@ -828,17 +931,17 @@ static hipError_t build_levels(const BuildWs &w, uint32_t n, float4 *wnodes, int
         // this batch's level counts, the counters (meta) and the RI bounds in one read
         // (a level cap below the batch size launches fewer levels: the read starts at level 0 then)
         const int l0 = wl > kLevelBatch ? wl - kLevelBatch : 0, nl = wl - l0;
-        uint32_t rb[kLevelBatch + 1 + 4 + 6];
+        uint32_t rb[kLevelBatch + 1 + kMetaRead + 6];
         BUILD_HIP(hipMemcpyAsync(rb, w.wlvl_cnt + l0, (size_t)(nl + 1) * 4, hipMemcpyDeviceToHost, s));
-        BUILD_HIP(hipMemcpyAsync(rb + kLevelBatch + 1, w.meta, 4 * 4, hipMemcpyDeviceToHost, s));
-        BUILD_HIP(hipMemcpyAsync(rb + kLevelBatch + 5, w.ri_bnd, 6 * 4, hipMemcpyDeviceToHost, s));
+        BUILD_HIP(hipMemcpyAsync(rb + kLevelBatch + 1, w.meta, kMetaRead * 4, hipMemcpyDeviceToHost, s));
+        BUILD_HIP(hipMemcpyAsync(rb + kLevelBatch + 1 + kMetaRead, w.ri_bnd, 6 * 4, hipMemcpyDeviceToHost, s));
         BUILD_HIP(hipStreamSynchronize(s));
         if (rb[nl] == 0) {
             int d = l0;
             while (d < wl && rb[d - l0] != 0) d++;
             out.depth = d;
-            for (int k = 0; k < 4; k++) out.meta[k] = rb[kLevelBatch + 1 + k];
-            for (int k = 0; k < 6; k++) out.bnd[k] = rb[kLevelBatch + 5 + k];
+            for (int k = 0; k < kMetaRead; k++) out.meta[k] = rb[kLevelBatch + 1 + k];
+            for (int k = 0; k < 6; k++) out.bnd[k] = rb[kLevelBatch + 1 + kMetaRead + k];
             break;
         }
         if (wl >= lvl_cap) return hipErrorNotSupported;
@@ -876,12 +979,14 @@ hipError_t inw_wide_build_device(const float4 *nodes, const uint32_t *lcnt, uint
 }
 
 hipError_t iow_cull_build_device(const float *hot, uint32_t n, void *ws, size_t ws_bytes, float4 *wide, float4 *obox,
-                                 IowCullDev &out, hipStream_t s, int max_levels) {
+                                 IowCullDev &out, hipStream_t s, int max_levels, const uint32_t *d_priors) {
     if (n < 2 || n >= 16384 || !hot || !ws || ws_bytes < inw_build_workspace_bytes(n) || !wide || !obox)
         return hipErrorInvalidValue;
     BuildWs w;
     carve(ws, n, &w);
     BUILD_HIP(build_begin(w, s));
+    // the priors' ten words ride in the counters' read-back (meta[4..13])
+    if (d_priors) BUILD_HIP(hipMemcpyAsync(w.meta + 4, d_priors, 10 * 4, hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(k_iow_boxes, dim3(nblk(n)), dim3(kB), 0, s, hot, n, obox, w.box, w.cen, w.ids, w.meta);
     BUILD_HIP(hipGetLastError());
     BuildLevels r;
@@ -889,7 +994,68 @@ hipError_t iow_cull_build_device(const float *hot, uint32_t n, void *ws, size_t 
     out.n_wide = r.meta[1];
     out.depth = r.depth;
     out.nonfinite = r.meta[0];
+    for (int k = 0; k < 10; k++) out.priors[k] = r.meta[4 + k];
     return hipSuccess;
+}
+
+// iow_prepare_device's workspace (256-B aligned pieces): the RI keys, the sorted keys, the mode's word,
+// the ten result words, the radix sort's own
+struct PrepWs {
+    uint32_t *keys, *sorted, *out;
+    unsigned long long *best;
+    void *tmp;
+    size_t tmp_bytes;
+};
+static size_t carve_prep(void *ws, uint32_t n, PrepWs *p) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char *q = static_cast<char *>(ws) + off;
+        off += (bytes + 255) & ~(size_t)255;
+        return static_cast<void *>(q);
+    };
+    PrepWs t{};
+    t.keys = static_cast<uint32_t *>(take((size_t)n * 4));
+    t.sorted = static_cast<uint32_t *>(take((size_t)n * 4));
+    t.best = static_cast<unsigned long long *>(take(8));
+    t.out = static_cast<uint32_t *>(take(16 * 4));
+    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, t.tmp_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n);
+    t.tmp = take(t.tmp_bytes);
+    if (p) *p = t;
+    return off;
+}
+
+size_t iow_prepare_workspace_bytes(uint32_t n) { return n ? carve_prep(reinterpret_cast<void *>(256), n, nullptr) : 0; }
+
+hipError_t iow_prepare_device(const float *types, const float *rec, uint32_t n, float *hot, float *cold, void *ws,
+                              size_t ws_bytes, const uint32_t **d_priors, hipStream_t s) {
+    if (!types || !rec || !n || n > 0x7fffffffu || !hot || !cold || !ws || ws_bytes < iow_prepare_workspace_bytes(n) ||
+        !d_priors || (reinterpret_cast<uintptr_t>(ws) & 255u))
+        return hipErrorInvalidValue;
+    PrepWs p;
+    carve_prep(ws, n, &p);
+    float4 *h4 = reinterpret_cast<float4 *>(hot), *c4 = reinterpret_cast<float4 *>(cold);
+    if (reinterpret_cast<uintptr_t>(rec) & 15u)
+        hipLaunchKernelGGL(k_iow_prepare<false>, dim3(nblk(n)), dim3(kB), 0, s, types, rec, n, h4, c4, p.keys);
+    else
+        hipLaunchKernelGGL(k_iow_prepare<true>, dim3(nblk(n)), dim3(kB), 0, s, types, rec, n, h4, c4, p.keys);
+    BUILD_HIP(hipGetLastError());
+    size_t tb = p.tmp_bytes;
+    BUILD_HIP(hipcub::DeviceRadixSort::SortKeys(p.tmp, tb, (const uint32_t *)p.keys, p.sorted, (int)n, 0, 32, s));
+    BUILD_HIP(hipMemsetAsync(p.best, 0, 8, s));
+    hipLaunchKernelGGL(k_iow_mode, dim3(nblk(n)), dim3(kB), 0, s, p.sorted, n, p.best);
+    hipLaunchKernelGGL(k_iow_priors, dim3(1), dim3(64), 0, s, p.sorted, n, p.best, p.out);
+    *d_priors = p.out;
+    return hipGetLastError();
+}
+
+hipError_t update_iow_kernel_info(int which, int info[4]) {
+    switch (which) {
+        case 0: return kernel_info(k_iow_prepare<true>, occupancy_of(k_iow_prepare<true>, kB), info);
+        case 1: return kernel_info(k_iow_prepare<false>, occupancy_of(k_iow_prepare<false>, kB), info);
+        case 2: return kernel_info(k_iow_mode, occupancy_of(k_iow_mode, kB), info);
+        case 3: return kernel_info(k_iow_priors, occupancy_of(k_iow_priors, 64), info);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 // The wide nodes without the repeated low planes (InwScene::cnodes): 7 float4 per node, lx ly lz

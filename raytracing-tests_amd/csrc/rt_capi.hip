@@ -456,6 +456,24 @@ int rt_dev_scene_iow03_update(rt_dev_scene *s, const float *types, const float *
     }
 }
 
+int rt_dev_scene_iow03_update_device(rt_dev_scene *s, const float *d_types, const float *d_records, uint32_t n, int flags,
+                                     void *stream, double timing_ms[4]) {
+    // argument errors come back before a device is touched, the scene untouched and still valid
+    if (!s || !d_types || !d_records || n == 0) return RT_E_ARG;
+    if ((flags & ~(RT_UPDATE_HOST_BUILD | RT_UPDATE_DEVICE_BUILD)) || flags == (RT_UPDATE_HOST_BUILD | RT_UPDATE_DEVICE_BUILD))
+        return RT_E_ARG;
+    if (s->kind != 3) return RT_E_UNSUPPORTED;
+    if (n > 0x7fffffffu) return RT_E_ARG;  // (the sort counts in an int)
+    HIP_OK(hipSetDevice(s->device));
+    HIP_OK(hipDeviceSynchronize());  // the scene's last frame may still read the buffers being replaced
+    try {  // the host builder of the fallback allocates: no exception crosses the ABI
+        return update_iow03_device(s, d_types, d_records, n, flags, static_cast<hipStream_t>(stream), timing_ms);
+    } catch (...) {
+        s->broken = true;
+        return RT_E_ARG;
+    }
+}
+
 int rt_dev_scene_set_options(rt_dev_scene *s, const rt_options *o) {
     if (!s || !options_ok(o)) return RT_E_ARG;
     const int wide = s->opt.inw_wide_walk, linear = s->opt.iow_linear;  // [build] options stay

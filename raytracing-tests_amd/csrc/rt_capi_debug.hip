@@ -498,6 +498,35 @@ int rt_debug_iow_dump(rt_dev_scene *s, uint32_t info[4], float *wide, float *obo
     return RT_OK;
 }
 
+int rt_debug_iow_prepare_host(const float *types, const float *records, uint32_t n, float *hot, float *cold,
+                              float priors[10]) {
+    if (!types || !records || n == 0) return RT_E_ARG;
+    try {
+        iow_prepare_host(types, records, n, hot, cold, priors);
+    } catch (...) {
+        return RT_E_ARG;
+    }
+    return RT_OK;
+}
+
+int rt_debug_iow_records(rt_dev_scene *s, float *hot, float *cold, float priors[10]) {
+    if (!s || s->kind != 3 || s->broken) return RT_E_ARG;
+    HIP_OK(hipSetDevice(s->device));
+    HIP_OK(hipDeviceSynchronize());
+    const size_t hb = size_t(s->n) * rtk::kIowHot * sizeof(float), cb = size_t(s->n) * rtk::kIowCold * sizeof(float);
+    if (s->hot.bytes < hb || s->cold.bytes < cb) return RT_E_ARG;  // never read past the allocation
+    if (hot) HIP_OK(hipMemcpy(hot, s->hot.p, hb, hipMemcpyDeviceToHost));
+    if (cold) HIP_OK(hipMemcpy(cold, s->cold.p, cb, hipMemcpyDeviceToHost));
+    if (priors) iow_priors_out(s->iow, priors);
+    return RT_OK;
+}
+
+int rt_debug_update_iow_kernel(int which, int info[4]) {
+    if (!info || which < 0 || which > 3) return RT_E_ARG;
+    HIP_OK(rtk::update_iow_kernel_info(which, info));
+    return RT_OK;
+}
+
 int rt_debug_trace_kernel(int any, int fused, int info[4]) {
     if (!info) return RT_E_ARG;
     HIP_OK(rtk::inw_trace_kernel_info(any != 0, fused != 0, info));

@@ -284,6 +284,12 @@ int update_inw(rt_dev_scene *s, const float *geom, uint32_t n, const float *node
 int update_inw_device(rt_dev_scene *s, const float *d_geom, uint32_t n, const float *d_aabbs, const float *d_lights,
                       uint32_t n_lights, int flags, hipStream_t st, double *ms);
 int update_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n, int flags, double *ms);
+int update_iow03_device(rt_dev_scene *s, const float *d_types, const float *d_rec, uint32_t n, int flags, hipStream_t st,
+                        double *ms);
+// make_iow03's hot / cold records (n * kIowHot, n * kIowCold floats; either may be null) and RI priors
+// of host records, no device; the priors as {ri_prior, alt_vals[8] (0 past the count), n_alt_vals}
+void iow_prepare_host(const float *types, const float *rec, uint32_t n, float *hot, float *cold, float priors[10]);
+void iow_priors_out(const IowCullPriors &q, float priors[10]);
 bool inw_sphere_records(const float *geom, uint32_t n, int layout, std::vector<float> &out);
 bool inw_textured(const float *geom, uint32_t n, int layout);
 bool textures_ok(const rt_texture *tex, int n_tex);

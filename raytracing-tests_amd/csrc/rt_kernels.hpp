@@ -338,13 +338,28 @@ hipError_t inw_wide_build_device(const float4 *nodes, const uint32_t *lcnt, uint
 // 2 <= n < 16384; ws holds inw_build_workspace_bytes(n).  Synchronises the stream (level counts).
 // hipErrorNotSupported: deeper than max_levels; nonfinite != 0: some box value is not finite (the
 // tree is then not to be used); in both cases the caller builds on the host.
+// d_priors (may be null): iow_prepare_device's ten result words, which then come back in the same copy
+// as the build's counts (priors; unwritten when the build returns an error).
 struct IowCullDev {
     uint32_t n_wide;
     int depth;
     uint32_t nonfinite;
+    uint32_t priors[10];
 };
 hipError_t iow_cull_build_device(const float *hot, uint32_t n, void *ws, size_t ws_bytes, float4 *wide, float4 *obox,
-                                 IowCullDev &out, hipStream_t s, int max_levels = 0);
+                                 IowCullDev &out, hipStream_t s, int max_levels = 0, const uint32_t *d_priors = nullptr);
+// An IOW-03 update from device-resident records (rt_build.hip): the hot (kIowHot floats) and
+// cold (kIowCold) records of the n objects at types (n) and rec (n * 24; any 4-byte alignment, float4 loads
+// when 16-byte aligned), byte-equal to iow_records (rt_scene_build.hip), and the RI priors of iow_priors
+// as ten words on the device at *d_priors (inside ws): {ri_prior, alt_vals[8], n_alt_vals as a float}, from
+// a radix sort of the RIs' orderable bits and a run-length pass.  ws: 256-byte aligned,
+// iow_prepare_workspace_bytes(n).  Never synchronises.
+size_t iow_prepare_workspace_bytes(uint32_t n);
+hipError_t iow_prepare_device(const float *types, const float *rec, uint32_t n, float *hot, float *cold, void *ws,
+                              size_t ws_bytes, const uint32_t **d_priors, hipStream_t s);
+// {VGPRs, scratch bytes, static LDS bytes, resident blocks per CU} of k_iow_prepare with float4 loads (which
+// = 0) and scalar loads (1), k_iow_mode (2), k_iow_priors (3)
+hipError_t update_iow_kernel_info(int which, int info[4]);
 // A scene update from device-resident records (rt_build.hip).  None of these synchronises
 // except inw_bin_trees_device (the level counts).
 // inw_prepare_device: the hot (kInwHot floats), cold (kInwCold) and sphere (12) records of the n GeometryBuff

@@ -1,7 +1,7 @@
 // rt_scene_build.hip -- scene construction: converts the reference's record layouts into the
 // kernels' device layouts (hot/cold split, per-object reciprocals hoisted under the numerics
 // contract), builds the sample tables, the walk structures (host and device builds) and the
-// textures, and redoes that per redraw (update_inw, update_inw_device, update_iow03).
+// textures, and redoes that per redraw (update_inw, update_inw_device, update_iow03, update_iow03_device).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -393,48 +393,61 @@ int make_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n
 // time), so that size keeps the host build and the next measured one is the threshold.
 constexpr uint32_t kIowDeviceBuildMin = 1024;
 
-// The next edit of an IOW-03 scene on its existing device buffers (rt_dev_scene_iow03_update; the
-// reference's CopyObjBuffer per ImGui edit, 03_Shadows_and_Materials/materials.cpp:329-364): new hot
-// and cold records, the RI priors, the object boxes and the culling BVH -- built on the device
-// (rtk::iow_cull_build_device) or by rtamd::iow_cull_build as make_iow03 builds it.
-// The sample tables, workspaces and speculation records stay.  ms[4]: host time of the records and
-// priors with their uploads, the boxes and the BVH, the upload of host-built structures, the call.
-int update_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n, int flags, double *ms) {
+namespace {
+
+// The two IOW-03 updates' clock: ms[0..2] by laps, ms[3] the whole call.
+struct UpdateClock {
     using clk = std::chrono::steady_clock;
-    const auto t_call = clk::now();
-    auto t = t_call;
-    auto lap = [&](int k) {
+    clk::time_point t_call = clk::now(), t = t_call;
+    double lap() {
         const auto now = clk::now();
-        if (ms) ms[k] = std::chrono::duration<double, std::milli>(now - t).count();
+        const double v = std::chrono::duration<double, std::milli>(now - t).count();
         t = now;
-    };
-    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
-    // Until every step below has succeeded the buffers may hold a mix of the old and the new scene:
-    // the scene refuses renders and queries and keeps its old n and counts, so nothing indexes past
-    // a buffer.  The new sizes are committed at the end.
-    s->broken = true;
+        return v;
+    }
+    double total() const { return std::chrono::duration<double, std::milli>(clk::now() - t_call).count(); }
+};
+
+// Where the records of an IOW-03 update live.  types / rec: on the host (rt_dev_scene_iow03_update), or
+// null with d_types / d_rec on the device and the priors' ten words at d_priors
+// (rt_dev_scene_iow03_update_device; the host builder then gets one copy-back, n * 25 floats).
+struct IowUpdateSrc {
+    const float *types, *rec;
+    const float *d_types, *d_rec;
+    const uint32_t *d_priors;
+};
+
+void set_priors(IowCullPriors &q, const uint32_t w[10]) {
+    q.ri_prior = __builtin_bit_cast(float, w[0]);
+    for (int v = 0; v < 8; v++) q.alt_vals[v] = __builtin_bit_cast(float, w[1 + v]);
+    q.n_alt_vals = int(__builtin_bit_cast(float, w[9]));
+}
+
+// What both updates do once the scene's hot and cold records are in place (enqueued on `st` or stored):
+// the object boxes and the culling BVH -- on the device (rtk::iow_cull_build_device) or
+// by rtamd::iow_cull_build as make_iow03 builds it, which is also the fallback of a device build that
+// ran past its level cap or met a box that is not finite -- then, for records on the device, the
+// priors' words (in the build's own read-back where the device build succeeded), the wait, and the
+// commit of the new sizes.  ms[1], ms[2], ms[3] as the two callers document them.
+int iow_update_finish(rt_dev_scene *s, const IowUpdateSrc &src, uint32_t n, int flags, hipStream_t st, UpdateClock &ck,
+                      double *ms) {
     IowCullPriors &q = s->iow;
-    std::vector<float> hot, cold;
-    iow_records(types, rec, n, hot, cold);
-    iow_priors(rec, n, q);
-    HIP_OK(s->hot.store(hot.data(), hot.size() * sizeof(float)));
-    HIP_OK(s->cold.store(cold.data(), cold.size() * sizeof(float)));
-    lap(0);
     // a scene created with iow_linear keeps the linear loop; n < 2 or n >= 16384 has no BVH, as
     // rtamd::iow_cull_build decides
     const bool bvh = !s->opt.iow_linear && n >= 2 && n < 16384;
     const bool device_build = flags == RT_UPDATE_DEVICE_BUILD || (flags == 0 && n >= kIowDeviceBuildMin);
     uint32_t n_wide = 0, built = 0;
     int depth = 0;
-    bool host_build = bvh && !device_build;
+    bool host_build = bvh && !device_build, have_priors = !src.d_priors;
+    uint32_t pw[10];
     if (bvh && device_build) {
         HIP_OK(s->nodes.reserve(size_t(n) * 8 * sizeof(float4)));
         HIP_OK(q.obox.reserve(size_t(n) * 6 * sizeof(float)));
         HIP_OK(q.build_ws.reserve(rtk::inw_build_workspace_bytes(n)));
         rtk::IowCullDev out{};
         const hipError_t be = rtk::iow_cull_build_device(s->hot.as<float>(), n, q.build_ws.p, q.build_ws.bytes,
-                                                         s->nodes.as<float4>(), q.obox.as<float4>(), out, nullptr,
-                                                         g_build_levels);
+                                                         s->nodes.as<float4>(), q.obox.as<float4>(), out, st,
+                                                         g_build_levels, src.d_priors);
         // deeper than the level cap (a chain-like scene), or a box that is not finite (the binned
         // splits mean nothing then): the host builder, whose scene equals a fresh one by construction
         if (be == hipErrorNotSupported) { built = 2; host_build = true; }
@@ -442,21 +455,36 @@ int update_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t
             HIP_OK(be);
             if (out.nonfinite) { built = 3; host_build = true; }
             else { built = 1; n_wide = out.n_wide; depth = out.depth; }
+            if (src.d_priors) { std::memcpy(pw, out.priors, sizeof(pw)); have_priors = true; }
         }
     }
+    double t_build = ck.lap(), t_up = 0.0;
+    if (!have_priors) HIP_OK(hipMemcpyAsync(pw, src.d_priors, sizeof(pw), hipMemcpyDeviceToHost, st));
     if (host_build) {
+        const float *types = src.types, *rec = src.rec;
+        std::vector<float> back;
+        if (!rec) {  // the one copy-back: types, then records
+            back.resize(size_t(n) * 25);
+            HIP_OK(hipMemcpyAsync(back.data(), src.d_types, size_t(n) * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(back.data() + n, src.d_rec, size_t(n) * 24 * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            types = back.data();
+            rec = back.data() + n;
+            t_up += ck.lap();
+        }
         rtamd::IowCull cull;
         if (!rtamd::iow_cull_build(types, rec, n, cull)) return RT_E_ARG;  // (bvh: it builds)
-        lap(1);
+        t_build += ck.lap();
         HIP_OK(s->nodes.store(cull.wide.data(), cull.wide.size() * sizeof(float)));
         HIP_OK(q.obox.store(cull.obox.data(), cull.obox.size() * sizeof(float)));
         n_wide = cull.n_wide;
         depth = cull.depth;
-        lap(2);
-    } else {
-        lap(1);
+        t_up += ck.lap();
     }
-    HIP_OK(hipDeviceSynchronize());  // every copy and build kernel: a render on any stream may follow
+    // every copy and build kernel: a render on any stream may follow
+    if (src.d_priors) HIP_OK(hipStreamSynchronize(st));
+    else HIP_OK(hipDeviceSynchronize());
+    if (src.d_priors) set_priors(q, pw);
     q.root_link = bvh ? 1 : 0;
     q.n_wide = n_wide;
     q.depth = depth;
@@ -464,8 +492,74 @@ int update_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t
     q.updates++;
     s->n = n;
     s->broken = false;
-    if (ms) ms[3] = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
+    if (ms) { ms[1] = t_build; ms[2] = t_up; ms[3] = ck.total(); }
     return RT_OK;
+}
+
+}  // namespace
+
+// The next edit of an IOW-03 scene on its existing device buffers (rt_dev_scene_iow03_update; the
+// reference's CopyObjBuffer per ImGui edit, 03_Shadows_and_Materials/materials.cpp:329-364): new hot
+// and cold records and the RI priors from the host's arrays, then the object boxes and the culling BVH
+// (iow_update_finish).  The sample tables, workspaces and speculation records stay.  ms[4]: host time of
+// the records and priors with their uploads, the boxes and the BVH, the upload of host-built structures,
+// the call.
+int update_iow03(rt_dev_scene *s, const float *types, const float *rec, uint32_t n, int flags, double *ms) {
+    UpdateClock ck;
+    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
+    // Until every step below has succeeded the buffers may hold a mix of the old and the new scene:
+    // the scene refuses renders and queries and keeps its old n and counts, so nothing indexes past
+    // a buffer.  The new sizes are committed at the end.
+    s->broken = true;
+    std::vector<float> hot, cold;
+    iow_records(types, rec, n, hot, cold);
+    iow_priors(rec, n, s->iow);
+    HIP_OK(s->hot.store(hot.data(), hot.size() * sizeof(float)));
+    HIP_OK(s->cold.store(cold.data(), cold.size() * sizeof(float)));
+    const double t0 = ck.lap();
+    if (ms) ms[0] = t0;
+    return iow_update_finish(s, IowUpdateSrc{types, rec, nullptr, nullptr, nullptr}, n, flags, nullptr, ck, ms);
+}
+
+// update_iow03 for types and records that live on the scene's device (rt_dev_scene_iow03_update_device,
+// DESIGN.md §5.18): the hot and cold records by k_iow_prepare, the priors by a sort of the RI keys and a
+// run-length pass, all on `st` in the scene's build workspace (the BVH build's pieces first, the
+// prepare's after them), then iow_update_finish on `st`.  With the device build no record byte crosses
+// to the host: ten words of priors come back with the build's counts.  ms[4]: host time of the records
+// and priors (their enqueue), the boxes and the BVH, the copy-back plus the upload of host-built
+// structures, the call.
+int update_iow03_device(rt_dev_scene *s, const float *d_types, const float *d_rec, uint32_t n, int flags, hipStream_t st,
+                        double *ms) {
+    UpdateClock ck;
+    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
+    s->broken = true;  // (as update_iow03: the new sizes are committed at the end)
+    IowCullPriors &q = s->iow;
+    HIP_OK(s->hot.reserve(size_t(n) * rtk::kIowHot * sizeof(float)));
+    HIP_OK(s->cold.reserve(size_t(n) * rtk::kIowCold * sizeof(float)));
+    const size_t build_bytes = rtk::inw_build_workspace_bytes(n), prep_bytes = rtk::iow_prepare_workspace_bytes(n);
+    HIP_OK(q.build_ws.reserve(build_bytes + prep_bytes));
+    const uint32_t *d_priors = nullptr;
+    HIP_OK(rtk::iow_prepare_device(d_types, d_rec, n, s->hot.as<float>(), s->cold.as<float>(),
+                                   static_cast<char *>(q.build_ws.p) + build_bytes, prep_bytes, &d_priors, st));
+    const double t0 = ck.lap();
+    if (ms) ms[0] = t0;
+    return iow_update_finish(s, IowUpdateSrc{nullptr, nullptr, d_types, d_rec, d_priors}, n, flags, st, ck, ms);
+}
+
+void iow_prepare_host(const float *types, const float *rec, uint32_t n, float *hot, float *cold, float priors[10]) {
+    std::vector<float> h, c;
+    iow_records(types, rec, n, h, c);
+    IowCullPriors q;
+    iow_priors(rec, n, q);
+    if (hot) std::memcpy(hot, h.data(), h.size() * sizeof(float));
+    if (cold) std::memcpy(cold, c.data(), c.size() * sizeof(float));
+    if (priors) iow_priors_out(q, priors);
+}
+
+void iow_priors_out(const IowCullPriors &q, float priors[10]) {
+    priors[0] = q.ri_prior;
+    for (int v = 0; v < 8; v++) priors[1 + v] = v < q.n_alt_vals ? q.alt_vals[v] : 0.0f;  // (slots past the count are stale)
+    priors[9] = float(q.n_alt_vals);
 }
 
 // Sphere records (rtk::InwScene::sph) when every object is an ellipsoid with equal scales and the

@@ -188,6 +188,11 @@ SIGNATURES = {
                                                  C.c_int, C.c_void_p, C.POINTER(C.c_double)]),
     "rt_inw_swept_boxes_async": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_dev_scene_iow03_update": (C.c_int, [C.c_void_p, _FP, _FP, C.c_uint32, C.c_int, C.POINTER(C.c_double)]),
+    "rt_dev_scene_iow03_update_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p,
+                                                   C.POINTER(C.c_double)]),
+    "rt_debug_iow_prepare_host": (C.c_int, [_FP, _FP, C.c_uint32, _FP, _FP, _FP]),
+    "rt_debug_iow_records": (C.c_int, [C.c_void_p, _FP, _FP, _FP]),
+    "rt_debug_update_iow_kernel": (C.c_int, [C.c_int, _IP]),
     "rt_debug_iow_info": (C.c_int, [C.c_void_p, _U32P]),
     "rt_debug_iow_dump": (C.c_int, [C.c_void_p, _U32P, _FP, _FP]),
     "rt_debug_path": (C.c_int, [C.c_void_p, C.POINTER(RtPathInfo)]),
@@ -1086,6 +1091,53 @@ def update_kernel_info(which: int) -> dict:
     """rt_debug_update_kernel: registers, scratch, LDS and resident blocks per CU of UPDATE_KERNELS[which]."""
     info = (C.c_int * 4)()
     check(load().rt_debug_update_kernel(int(which), info), "rt_debug_update_kernel")
+    return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
+
+
+def update_iow03_device(handle, d_types, d_records, n: int, flags: int = 0, stream=None) -> list:
+    """rt_dev_scene_iow03_update_device: the next edit of the IOW-03 device scene `handle` from device
+    buffers (pointers or torch tensors): d_types n floats, d_records n * 24; flags 0, RT_UPDATE_HOST_BUILD
+    or RT_UPDATE_DEVICE_BUILD.  Returns timing_ms: host ms of [records and priors, boxes and culling BVH,
+    copy-back + upload of host-built structures, the whole call]."""
+    tm = (C.c_double * 4)()
+    check(load().rt_dev_scene_iow03_update_device(handle, _dptr(d_types), _dptr(d_records), int(n), int(flags), stream,
+                                                  tm), "rt_dev_scene_iow03_update_device")
+    return list(tm)
+
+
+IOW_HOT_FLOATS, IOW_COLD_FLOATS = 20, 8
+
+
+def iow_prepare_host(types: np.ndarray, records: np.ndarray) -> dict:
+    """rt_debug_iow_prepare_host: the host packer's hot (n, 20) and cold (n, 8) records and the RI priors
+    (10 floats: ri_prior, alt_vals[8], n_alt_vals) of IOW-03 types (n) and records (n, 24).  No device."""
+    types = np.ascontiguousarray(types, np.float32)
+    records = np.ascontiguousarray(records, np.float32)
+    n = len(types)
+    hot, cold = np.zeros((n, IOW_HOT_FLOATS), np.float32), np.zeros((n, IOW_COLD_FLOATS), np.float32)
+    priors = np.zeros(10, np.float32)
+    check(load().rt_debug_iow_prepare_host(fptr(types), fptr(records), n, fptr(hot), fptr(cold), fptr(priors)),
+          "rt_debug_iow_prepare_host")
+    return {"hot": hot, "cold": cold, "priors": priors}
+
+
+def iow_records(handle) -> dict:
+    """rt_debug_iow_records: the current hot records, cold records and priors of an IOW-03 device scene, in
+    iow_prepare_host's keys."""
+    n = iow_info(handle)["objects"]
+    hot, cold = np.zeros((n, IOW_HOT_FLOATS), np.float32), np.zeros((n, IOW_COLD_FLOATS), np.float32)
+    priors = np.zeros(10, np.float32)
+    check(load().rt_debug_iow_records(handle, fptr(hot), fptr(cold), fptr(priors)), "rt_debug_iow_records")
+    return {"hot": hot, "cold": cold, "priors": priors}
+
+
+UPDATE_IOW_KERNELS = ("k_iow_prepare float4 loads", "k_iow_prepare scalar loads", "k_iow_mode", "k_iow_priors")
+
+
+def update_iow_kernel_info(which: int) -> dict:
+    """rt_debug_update_iow_kernel: registers, scratch, LDS and resident blocks per CU of UPDATE_IOW_KERNELS[which]."""
+    info = (C.c_int * 4)()
+    check(load().rt_debug_update_iow_kernel(int(which), info), "rt_debug_update_iow_kernel")
     return dict(zip(("vgprs", "scratch_bytes", "lds_bytes", "blocks_per_cu"), list(info)))
 
 
